@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Benchmark: seconds of audio enhanced per second, UNIVERSE++ 16 kHz, 8 s clips.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(``--dump-outputs DIR`` also writes what the last timed step returned).
+``--full`` adds the legs under "Extra fields" below, each a run of its own
+after the timed steps.
 
 One step = one ``model.enhance()`` of one synthetic 8 s clip at batch 1
 (BASELINE.json configs[1]: "UNIVERSE++ 16 kHz, batch=1, 8 s clips"), run as
@@ -16,7 +21,7 @@ Ranks: under torchrun (WORLD_SIZE set) this process is one rank.  Without it,
 ``--gpus N`` (N > 1) starts the N rank processes itself before touching the
 GPU (``launch_ranks``), each with the torchrun environment, and waits for them.
 
-Extra fields:
+Extra fields (``--full`` only; each has a --no-... switch):
   roofline      the dominant kernel (ou_conv, every launch of one enhance):
                 algorithmic FLOPs of the reference ops it replaces and
                 algorithmic bytes (activations once, f32 weights) over its
@@ -295,11 +300,37 @@ def timed_loop(step, warmup, steps, world, sync):
     return max_over_ranks(time.perf_counter() - t0)
 
 
+DUMP_MAX_BYTES = 64 * 2**20   # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(dirname, rank, world, out):
+    """Write what the last timed step returned (the enhanced clips of this
+    rank, [B, T]) as float32 ``enhanced.npy`` (``enhanced_rank<r>.npy`` on
+    the other ranks).  An output past this rank's share of DUMP_MAX_BYTES is
+    stored as a fixed sample of its flattened values (seeded by the element
+    count alone, so two builds sample the same positions)."""
+    import numpy as np
+
+    a = out.detach().to("cpu").float().numpy()
+    cap = DUMP_MAX_BYTES // max(world, 1) // 4 - 64   # elements; 64 left for the .npy header
+    if a.size > cap:
+        idx = np.sort(np.random.default_rng(a.size).integers(0, a.size, size=cap))
+        a = a.reshape(-1)[idx]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "enhanced.npy" if rank == 0 else f"enhanced_rank{rank}.npy"),
+            np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the extra legs: the per-op profile / roofline, the f32 "
+                         "pass, the queued leg and the CPU baseline (each has a --no-... switch); off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/enhanced.npy (float32)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS),
                     help="BASELINE.json config (c2 = configs[1], the headline)")
     ap.add_argument("--seconds", type=float, default=None, help="override the config's clip length")
@@ -322,6 +353,10 @@ def main():
                          "profiles/pmc_latest.json for c2, profiles/pmc_latest_<config>.json for the others")
     ap.add_argument("--stub-ms", type=float, default=None, help=argparse.SUPPRESS)  # CPU test of the launcher
     args = ap.parse_args()
+    if not args.full:
+        if args.dump_ops:
+            ap.error("--dump-ops writes the per-op profile: it needs --full")
+        args.no_cpu_baseline = args.no_profile = args.no_queued = args.no_f32_pass = True
     if args.traffic_json is None:
         args.traffic_json = default_traffic_json(args.config)
 
@@ -391,9 +426,15 @@ def main():
     ekw = {"n_steps": C["n_steps"]} if C["n_steps"] else {}
     sync = lambda: torch.cuda.synchronize(dev)
 
+    last = [None]   # what the latest step returned (--dump-outputs)
+
+    def step(i):
+        last[0] = model.enhance(clips[i % len(clips)], rng=rng, **ekw)
+
     with torch.no_grad():
-        elapsed = timed_loop(lambda i: model.enhance(clips[i % len(clips)], rng=rng, **ekw),
-                             args.warmup, args.steps, world, sync)
+        elapsed = timed_loop(step, args.warmup, args.steps, world, sync)
+    if args.dump_outputs and last[0] is not None:
+        dump_outputs(args.dump_outputs, rank, world, last[0])
 
     prof = None
     if not args.no_profile:

@@ -1,3 +1,5 @@
+import glob
+import io
 import os
 import sys
 
@@ -21,9 +23,72 @@ def pytest_configure(config):
         torch.set_num_threads(max(1, (os.cpu_count() or 1) // n))
 
 
+PART_BYTES = 1000 * 1024   # no fixture file reaches 1 MiB
+
+
 def load_golden(tag):
-    with np.load(os.path.join(GOLDEN, f"{tag}.npz"), allow_pickle=False) as f:
-        return {k: f[k] for k in f.files}
+    """The arrays of fixture ``tag``: ``<tag>.npz``, or, for a fixture that
+    would pass PART_BYTES as one file, its parts ``<tag>.00.npz``,
+    ``<tag>.01.npz``, ... (save_golden).  A part holds whole arrays under
+    their names and, of an array too large for one part, flattened slices
+    ``name@0``, ``name@1``, ... beside ``name@shape``; the arrays come back
+    bit for bit, in the order they were saved."""
+    paths = [os.path.join(GOLDEN, f"{tag}.npz")]
+    if not os.path.exists(paths[0]):
+        paths = sorted(glob.glob(os.path.join(GOLDEN, f"{tag}.[0-9][0-9].npz")))
+        if not paths:
+            raise FileNotFoundError(f"no golden fixture {tag!r} under {GOLDEN}")
+    out, pieces = {}, {}
+    for p in paths:
+        with np.load(p, allow_pickle=False) as f:
+            for k in f.files:
+                if "@" in k:
+                    name, i = k.split("@")
+                    out.setdefault(name, None)   # keeps the array's place in the order
+                    pieces.setdefault(name, {})[i] = f[k]
+                else:
+                    out[k] = f[k]
+    for name, ps in pieces.items():
+        shape = tuple(int(s) for s in ps.pop("shape"))
+        out[name] = np.concatenate([ps[str(i)] for i in range(len(ps))]).reshape(shape)
+    return out
+
+
+def _npz_bytes(arrays):
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    return buf.getbuffer().nbytes
+
+
+def save_golden(tag, arrays):
+    """Write fixture ``tag`` for load_golden: one ``<tag>.npz`` if it stays
+    under PART_BYTES, else numbered parts that each do (tests/golden/make_golden.py)."""
+    items = []   # (key, array, compressed bytes), in the arrays' order
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        c = _npz_bytes({name: a})
+        if c <= PART_BYTES // 2:
+            items.append((name, a, c))
+            continue
+        n = -(-c // (PART_BYTES // 2))   # slices of about half a part each
+        flat = np.ascontiguousarray(a).reshape(-1)
+        items.append((f"{name}@shape", np.asarray(a.shape, dtype=np.int64), 512))
+        for i, s in enumerate(np.array_split(flat, n)):
+            items.append((f"{name}@{i}", s, _npz_bytes({f"{name}@{i}": s})))
+    parts, size = [{}], 0
+    for k, a, c in items:
+        if parts[-1] and size + c > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += c
+    for old in [os.path.join(GOLDEN, f"{tag}.npz")] + glob.glob(os.path.join(GOLDEN, f"{tag}.[0-9][0-9].npz")):
+        if os.path.exists(old):
+            os.remove(old)
+    for i, part in enumerate(parts):
+        p = os.path.join(GOLDEN, f"{tag}.npz" if len(parts) == 1 else f"{tag}.{i:02d}.npz")
+        np.savez_compressed(p, **part)
+        assert os.path.getsize(p) <= PART_BYTES, (p, os.path.getsize(p))
 
 
 def golden_state_dict(d, seed=0):

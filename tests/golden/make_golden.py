@@ -36,6 +36,9 @@ from open_universe_amd.configs import get_config  # noqa: E402
 from open_universe_amd.utils.synthetic import RC_DAMP, fill_module_, synth_audio  # noqa: E402
 from oracle import ou_oracle  # noqa: E402  (only for the torchaudio restatement)
 
+sys.path.insert(0, os.path.dirname(HERE))
+from conftest import load_golden, save_golden  # noqa: E402  (fixtures are stored in parts under 1 MiB)
+
 
 # ---------------------------------------------------------------------------
 # stand-ins for third-party packages missing from the image
@@ -408,7 +411,7 @@ def make_metric_cases():
     lsd_mod = _load("ouref.metrics.lsd", REF + "/metrics/lsd.py")
     d = {}
     g = torch.Generator().manual_seed(77)
-    pp = np.load(os.path.join(HERE, "pp16_c4.npz"))
+    pp = load_golden("pp16_c4")
     for fs in (16000, 24000):
         n = int(0.75 * fs)
         clean = torch.from_numpy(np.stack([synth_audio(n, fs, 40 + i)[1] for i in range(3)])).double()
@@ -435,16 +438,16 @@ def main():
     load_reference()
     want = set(sys.argv[1:])
     if "metrics" in want:
-        np.savez_compressed(os.path.join(HERE, "metrics.npz"), **make_metric_cases())
+        save_golden("metrics", make_metric_cases())
         want.discard("metrics")
         if not want:
             return
     for name, nch, T, tag in CASES:
         if want and tag not in want:
             continue
-        np.savez_compressed(os.path.join(HERE, f"{tag}.npz"), **make_model_case(name, nch, T, tag))
+        save_golden(tag, make_model_case(name, nch, T, tag))
     if not want or "gru" in want:
-        np.savez_compressed(os.path.join(HERE, "gru.npz"), **make_gru_cases())
+        save_golden("gru", make_gru_cases())
     # full-width manifests (state-dict names/shapes, EMA order)
     if not want or "manifests" in want:
         for name in ("pp24", "orig16"):

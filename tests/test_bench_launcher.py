@@ -47,6 +47,27 @@ def test_rank_batch():
         raise AssertionError("32 clips over 3 ranks must be refused")
 
 
+def test_dump_outputs_float32_capped_and_repeatable(tmp_path, monkeypatch):
+    """--dump-outputs: the step's output as float32 .npy; past the size cap a
+    fixed sample of it, the same positions on every call."""
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+
+    import bench
+
+    x = torch.arange(2 * 1 * 50, dtype=torch.float64).reshape(2, 1, 50)
+    bench.dump_outputs(str(tmp_path / "a"), 0, 1, x)
+    a = np.load(tmp_path / "a" / "enhanced.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 1, 50) and np.array_equal(a, x.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * (64 + 40))   # room for 40 values
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), 1, 1, x)
+    b, c = (np.load(tmp_path / d / "enhanced_rank1.npy") for d in ("b", "c"))
+    assert b.dtype == np.float32 and b.shape == (40,) and np.array_equal(b, c)
+    assert np.isin(b, x.numpy()).all() and (tmp_path / "b" / "enhanced_rank1.npy").stat().st_size <= 4 * (64 + 40)
+
+
 def test_default_traffic_json_per_config():
     """bench quotes `traffic` from the PMC summary of its own config: the
     headline's pmc_latest.json, pmc_latest_<config>.json otherwise; the

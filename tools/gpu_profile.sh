@@ -19,7 +19,7 @@ export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 export OUHIP_TUNE_CACHE="$O/tune_$TAG.json"
 B="$ROOT/bench.py"
 read -r -a EXTRA <<< "${BENCH_EXTRA:-}"
-timeout -k 10 600 python3 "$B" --config "$CFG" "${EXTRA[@]}" "${FIRST[@]}" --dump-ops "$O/ops_$TAG.json" \
+timeout -k 10 600 python3 "$B" --full --config "$CFG" "${EXTRA[@]}" "${FIRST[@]}" --dump-ops "$O/ops_$TAG.json" \
     > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err" &&
 cd /tmp &&
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_$TAG" -o kt -- \

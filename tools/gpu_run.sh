@@ -7,7 +7,7 @@
 #   tests:FILE[::T]  one test file / test
 #   profile:CFG      tools/gpu_profile.sh (bench line, kernel trace, FETCH/WRITE PMC passes)
 #   levels:CFG       tools/gpu_level_pmc.sh (per-op conv-stack table)
-#   bench:CFG        bench.py --config CFG, default arguments (the driver's line)
+#   bench:CFG        bench.py --full --config CFG, default arguments otherwise (the line with every extra leg)
 #   benchpmc:CFG     profile:CFG, then bench:CFG quoting `traffic` from that PMC summary
 #   shards           C4 at the per-rank batches of 2/4/8 GPUs (B = 16, 8, 4)
 #   c4u              C4 on the undamped synthetic weights (exponents widen in the warm-up)
@@ -33,7 +33,7 @@ export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 line() { python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[1], d['value'], d['unit'], d['ms_per_step'], d.get('profile'), d.get('fallbacks'))" "$1"; }
 bench() {   # bench OUT LIMIT ARGS...
     local out=$1 lim=$2; shift 2
-    timeout -k 10 "$lim" python3 bench.py "$@" > "$out.json" 2> "$out.err" || { tail -20 "$out.err"; return 1; }
+    timeout -k 10 "$lim" python3 bench.py --full "$@" > "$out.json" 2> "$out.err" || { tail -20 "$out.err"; return 1; }
     line "$out.json"
 }
 for step in "$@"; do
