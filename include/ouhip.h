@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define OUHIP_ABI_VERSION 8
+#define OUHIP_ABI_VERSION 9
 
 int ou_abi_version(void);
 const char* ou_last_error(void);
@@ -623,6 +623,112 @@ int ou_program_profile(ou_program* p, void* stream, float* ms);
  * (synchronises).  The concurrent timeline of the lane schedule
  * (tools/critical_path.py). */
 int ou_program_trace(ou_program* p, void* stream, float* t0, float* t1);
+
+/* ------------------------------------------------------------------------
+ * Sampler noise: a counter-based normal stream of the project's own (it does
+ * not reproduce torch.randn).  Philox4x32-10 with key = (seed low, seed high)
+ * and counter = (q low, q high, 0, 0), q = offset + i / 4: counter q yields
+ * out[4 (q - offset) .. + 4).  From the four words x0..x3,
+ *   u1 = ((x0 >> 8) + 1) 2^-24,  u2 = (x1 >> 8) 2^-24      (exact in f32)
+ *   r = sqrtf(-2 logf(u1)),  z0 = r cospif(2 u2),  z1 = r sinpif(2 u2)
+ * and (x2, x3) give (z2, z3) the same way.  ou_randn launches one kernel on
+ * ``stream``; ou_philox4x32 is the generator's block function on the host
+ * (10 rounds, Random123's known answers).
+ * ---------------------------------------------------------------------- */
+int ou_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream);
+int ou_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+
+/* ------------------------------------------------------------------------
+ * Exported enhance bundles: one recorded enhance program for a fixed
+ * (batch, length, options) in a relocatable file (written by
+ * open_universe_amd/bundle.py), replayed without Python.
+ *
+ * File layout (little-endian; every section starts on a 64-byte boundary):
+ *   header, 128 bytes
+ *       0 char[4] "OUHB"    4 u32 format version (1)   8 u32 OUHIP_ABI_VERSION
+ *      12 u32 regions      16 u32 ops                 20 u32 relocations
+ *      24 u32 JSON bytes   28 u32 0                   32 char[16] arch ("gfx950")
+ *      48 u64 region table 56 u64 op table            64 u64 relocation table
+ *      72 u64 I/O table    80 u64 JSON                88 u64 file bytes
+ *      96 u64 FNV-1a (64 bit) of bytes [0, 96) then [128, end of tables)
+ *     104 u64 end of tables: the header, the tables, the descriptors and the
+ *         JSON lie below it, the regions' saved bytes from it on
+ *     112 .. 127 zero
+ *   region table, 32 bytes each: u32 kind (0 arena, 1 saved, 2 zero-filled),
+ *       u32 0, u64 bytes, u64 file offset of the saved bytes (0 if none), u64 0.
+ *       Region 0 is the plan's arena.  Every region is writable device memory
+ *       after load, based on a 256-byte boundary; kinds 0 and 2 start zeroed.
+ *   op table, 64 bytes each: u32 OU_OP_* kind, u32 descriptor bytes, u64 file
+ *       offset of the descriptor, u32 first relocation, u32 relocation count,
+ *       char[40] label (NUL-terminated).  The stored descriptors hold 0 in
+ *       every relocated field.
+ *   relocation table, 24 bytes each, grouped by op in op order: u32 op,
+ *       u32 byte offset in the descriptor (8-byte pointer field), u32 region,
+ *       u32 0, u64 offset in the region.
+ *   I/O table, 4 entries (mix, noise, out, status) of 32 bytes: u32 region,
+ *       u32 count (noise draws; status words; else 0), u64 offset in the
+ *       region, u32 batch, u32 samples per item (noise: padded), u64 0.
+ *   JSON (UTF-8): fs, n_steps, epsilon, keep_rms, conv_prec, config.
+ *
+ * Host layer (no HIP call): open validates everything -- versions, every
+ * table entry inside the file, descriptor sizes, every relocation inside its
+ * descriptor and its region, the lane structure -- so that a file that opens
+ * can be materialised at any set of region bases.
+ * ---------------------------------------------------------------------- */
+typedef struct ou_bundle ou_bundle;
+typedef struct ou_model ou_model;
+
+typedef struct ou_bundle_io {
+    int32_t region;            /* region the buffer lies in                     */
+    int32_t count;             /* noise: draws; status: int32 words; else 0     */
+    int64_t offset;            /* byte offset in the region                     */
+    int32_t batch;             /* batch items (0 for status)                    */
+    int32_t length;            /* samples per item (noise: the padded length)   */
+} ou_bundle_io;
+
+typedef struct ou_bundle_meta {
+    ou_bundle_io mix;          /* float [batch][length], written by the host    */
+    ou_bundle_io noise;        /* float [count][batch][length]                  */
+    ou_bundle_io out;          /* float [batch][length], the result             */
+    ou_bundle_io status;       /* int32 [count]: [0] GRU hand-off timeout,
+                                  [1] and [4..] split-f16 range codes           */
+    int32_t n_regions, n_ops;
+    int64_t region_bytes;      /* device memory a load allocates, in total      */
+    const char* json;          /* NUL-terminated, owned by the handle           */
+    int64_t json_bytes;
+    char arch[16];
+} ou_bundle_meta;
+
+int ou_bundle_open(const char* path, ou_bundle** out);
+void ou_bundle_close(ou_bundle* b);
+int ou_bundle_info(const ou_bundle* b, ou_bundle_meta* meta);
+/* Region i: its kind and size; *data = its saved bytes inside the mapped
+ * file (valid until close), NULL for a region that starts zeroed.          */
+int ou_bundle_region(const ou_bundle* b, int i, int32_t* kind, int64_t* bytes, const void** data);
+/* Op i: its OU_OP_* kind, descriptor size and label (owned by the handle). */
+int ou_bundle_op(const ou_bundle* b, int i, int32_t* kind, int64_t* desc_bytes, const char** label);
+/* Copy op `op`'s descriptor to desc_out with every relocated field set to
+ * region_bases[region] + offset (region_bases: one address per region).    */
+int ou_bundle_materialize(const ou_bundle* b, const uint64_t* region_bases, int op, void* desc_out);
+
+/* Device layer: the model-level ABI.  A load allocates every region
+ * (hipMalloc), uploads the saved bytes, zeroes the rest, builds the program
+ * and, with capture != 0, captures it as one hipGraph; nothing allocates
+ * after it.  mix, noise and out are device pointers laid out as
+ * ou_bundle_meta describes; the copies in and out and the replay are ordered
+ * on ``stream``.  Calls on one handle are not re-entrant.  ou_model_enhance
+ * draws the noise with ou_randn (seed, offset) into the noise buffer on the
+ * same stream, ahead of the replay and outside the captured graph.
+ * ou_model_status waits for the stream last used, reads the status words
+ * and zeroes them: 0 clean, 1 GRU hand-off timeout, 2 split-f16 range error
+ * (the output is undefined: use a bundle exported with f32 operands),
+ * < 0 on a HIP error.                                                       */
+int ou_bundle_load(const char* path, int capture, ou_model** out);
+int ou_model_enhance_noise(ou_model* m, const float* mix, const float* noise, float* out, void* stream);
+int ou_model_enhance(ou_model* m, const float* mix, float* out, uint64_t seed, uint64_t offset, void* stream);
+int ou_model_status(ou_model* m);
+int ou_model_info(const ou_model* m, ou_bundle_meta* meta);
+void ou_model_destroy(ou_model* m);
 
 #ifdef __cplusplus
 }

@@ -8,11 +8,11 @@ library is missing, every compute entry point raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, c_char, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OUHIP_LIB", os.path.join(_HERE, "libouhip.so"))
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 fp = c_void_p  # device pointers are passed as integers
 
@@ -153,6 +153,17 @@ class BlockDesc(ctypes.Structure):
     ]
 
 
+class BundleIo(ctypes.Structure):
+    _fields_ = [("region", c_int32), ("count", c_int32), ("offset", c_int64),
+                ("batch", c_int32), ("length", c_int32)]
+
+
+class BundleMeta(ctypes.Structure):
+    _fields_ = [("mix", BundleIo), ("noise", BundleIo), ("out", BundleIo), ("status", BundleIo),
+                ("n_regions", c_int32), ("n_ops", c_int32), ("region_bytes", c_int64),
+                ("json", c_char_p), ("json_bytes", c_int64), ("arch", c_char * 16)]
+
+
 OP_STRUCT = {
     OP_CONV: ConvDesc, OP_GRU: GruDesc, OP_EMBED: EmbedDesc, OP_HEAD: HeadDesc,
     OP_NORMALIZE: NormArgs, OP_INV_RMS: RmsArgs, OP_RMS: RmsArgs, OP_POWER: PowerArgs,
@@ -220,6 +231,20 @@ EXPORTS = {
     "ou_program_op_kind": (c_int, [c_void_p, c_int]),
     "ou_program_profile": (c_int, [c_void_p, c_void_p, POINTER(c_float)]),
     "ou_program_trace": (c_int, [c_void_p, c_void_p, POINTER(c_float), POINTER(c_float)]),
+    "ou_randn": (c_int, [fp, c_int64, c_uint64, c_uint64, c_void_p]),
+    "ou_philox4x32": (c_int, [POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]),
+    "ou_bundle_open": (c_int, [c_char_p, POINTER(c_void_p)]),
+    "ou_bundle_close": (None, [c_void_p]),
+    "ou_bundle_info": (c_int, [c_void_p, POINTER(BundleMeta)]),
+    "ou_bundle_region": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_void_p)]),
+    "ou_bundle_op": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_char_p)]),
+    "ou_bundle_materialize": (c_int, [c_void_p, POINTER(c_uint64), c_int, c_void_p]),
+    "ou_bundle_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
+    "ou_model_enhance_noise": (c_int, [c_void_p, fp, fp, fp, c_void_p]),
+    "ou_model_enhance": (c_int, [c_void_p, fp, fp, c_uint64, c_uint64, c_void_p]),
+    "ou_model_status": (c_int, [c_void_p]),
+    "ou_model_info": (c_int, [c_void_p, POINTER(BundleMeta)]),
+    "ou_model_destroy": (None, [c_void_p]),
 }
 
 _lib = None

@@ -21,10 +21,11 @@ cc() {   # cc <src> <obj> [extra flags...]
   /opt/rocm/bin/hipcc "${CFLAGS[@]}" ${OUHIP_CFLAGS:-} "$@" -c "$HERE/$src" -o "$OBJDIR/$obj" &
   pids+=($!)
 }
-for s in ou_gru.hip ou_misc.hip ou_program.hip ou_audio.hip ou_block.hip; do
+for s in ou_gru.hip ou_misc.hip ou_program.hip ou_audio.hip ou_block.hip ou_rand.hip ou_model.hip; do
   cc "$s" "${s%.hip}.o"
 done
 cc ou_flac.cpp ou_flac.o   # host-only (FLAC input decoding for the CLI)
+cc ou_bundle.cpp ou_bundle.o   # host-only (the exported bundles' file parser)
 if [[ "${OUHIP_CFLAGS:-}" == *OU_CONV_STAMPS* ]]; then
   cc ou_conv.hip ou_conv.o
 else
