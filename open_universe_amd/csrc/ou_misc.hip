@@ -71,9 +71,12 @@ __device__ float block_max(float v, float* red)
 
 // ---------------------------------------------------------------- embedding
 // g for one sigma per workgroup -> gbuf[i][dim]
+// SigmaBlock layers ping-pong between two LDS buffers of kEmbedMax floats:
+// the widest layer (8 n_rff) and dim must fit one (checked by ou_embed)
+constexpr int kEmbedMax = 1024;
 __global__ __launch_bounds__(256) void embed_g_kernel(ou_embed_desc d, float* gbuf)
 {
-    __shared__ float s0[1024], s1[1024];
+    __shared__ float s0[kEmbedMax], s1[kEmbedMax];
     const int i = blockIdx.x;
     const float ls = log10f(d.sigma[i]);
     float* g = gbuf + (int64_t)i * d.dim;
@@ -412,10 +415,18 @@ __global__ __launch_bounds__(256) void sigmed_pick_kernel(const float* x, float*
 //   snake: v = u + sin(a u)^2 / (a + 1e-9)
 //   down2: y[t] = sum_k kd[k] * v[2t + k - wd]              (torchaudio Resample 2->1)
 constexpr int kSnakeTile = 256;
+// the longest filters ou_snake_aa accepts, and the LDS extents they need: a
+// tile reads nv = 2 (tile - 1) + taps_down up-sampled values, which stage
+// nv / 2 + taps_up + 2 input samples (highest index read: nv / 2 + taps_up - 1)
+constexpr int kSnakeMaxUp = 32, kSnakeMaxDown = 64;
+constexpr int kSnakeNv = 2 * (kSnakeTile - 1) + kSnakeMaxDown;
+constexpr int kSnakeNs = kSnakeNv / 2 + kSnakeMaxUp + 2;
+static_assert(2 * (kSnakeTile - 1) + kSnakeMaxDown <= kSnakeNv && kSnakeNv / 2 + kSnakeMaxUp + 2 <= kSnakeNs,
+              "snake_aa_kernel: LDS arrays shorter than the accepted filters need");
 __global__ __launch_bounds__(256) void snake_aa_kernel(ou_snake_desc d)
 {
-    __shared__ float sh[kSnakeTile + 64];
-    __shared__ float sv[2 * kSnakeTile + 64];
+    __shared__ float sh[kSnakeNs];
+    __shared__ float sv[kSnakeNv];
     const int c = blockIdx.y, b = blockIdx.z;
     const int t0 = blockIdx.x * kSnakeTile;
     const int T = d.length;
@@ -464,10 +475,18 @@ inline unsigned blocks_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) /
 
 extern "C" int ou_embed(const ou_embed_desc* d, void* stream)
 {
-    if (!d || !d->sigma || !d->out || !d->w || !d->gbuf || d->n <= 0)
+    if (!d || !d->sigma || !d->out || !d->w || !d->bias || !d->gbuf || d->n <= 0 || d->dim <= 0 || d->rows <= 0)
         return ou_fail(-1, "embed: invalid descriptor");
-    if (d->kind == 1 && (d->n_rff * 2 > 1024 || d->dim > 1024 || !d->rff_freq))
-        return ou_fail(-1, "embed: bad SigmaBlock sizes");
+    if (d->kind != 0 && d->kind != 1) return ou_fail(-1, "embed: unknown kind %d", d->kind);
+    if (d->kind == 0 && (d->dim & 1))
+        return ou_fail(-1, "embed: SimpleTimeEmbedding needs an even dim");   // sin | cos halves
+    if (d->kind == 1) {
+        // layer widths 2 n_rff -> 4 n_rff -> 8 n_rff -> dim, each held in one LDS buffer
+        if (d->n_rff <= 0 || d->n_rff > kEmbedMax / 8 || d->dim > kEmbedMax || !d->rff_freq)
+            return ou_fail(-1, "embed: bad SigmaBlock sizes (n_rff <= %d, dim <= %d)", kEmbedMax / 8, kEmbedMax);
+        for (int l = 0; l < 3; ++l)
+            if (!d->mlp_w[l] || !d->mlp_b[l]) return ou_fail(-1, "embed: SigmaBlock layer %d has no weights", l);
+    }
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(embed_g_kernel, dim3(d->n), dim3(256), 0, s, *d, d->gbuf);
     int rc = ou_check_launch("embed_g");
@@ -479,7 +498,7 @@ extern "C" int ou_embed(const ou_embed_desc* d, void* stream)
 
 extern "C" int ou_head(const ou_head_desc* d, void* stream)
 {
-    if (!d || !d->h || !d->w || !d->out || d->length <= 0 || d->batch <= 0)
+    if (!d || !d->h || !d->w || !d->out || d->channels <= 0 || d->length <= 0 || d->batch <= 0)
         return ou_fail(-1, "head: invalid descriptor");
     if (d->mode != 0 && !d->x) return ou_fail(-1, "head: sampler mode needs x");
     if (d->mode == 1 && !d->z) return ou_fail(-1, "head: step mode needs z");
@@ -517,7 +536,7 @@ extern "C" int ou_rms(const float* x, float* out, int batch, int64_t n, void* st
 extern "C" int ou_power(const float* x, float* y, int batch, int nf, int frames, void* stream)
 {
     const int64_t total = (int64_t)batch * nf * frames;
-    if (!x || !y || total <= 0) return ou_fail(-1, "power: bad args");
+    if (!x || !y || batch <= 0 || nf <= 0 || frames <= 0) return ou_fail(-1, "power: bad args");
     hipLaunchKernelGGL(power_kernel, dim3(blocks_for(total, 256)), dim3(256), 0,
                        (hipStream_t)stream, x, y, nf, frames, total);
     return ou_check_launch("power");
@@ -527,7 +546,7 @@ extern "C" int ou_pad(const float* x, int64_t x_bstride, float* y, int batch, in
                       int left, void* stream)
 {
     const int64_t total = (int64_t)batch * n_out;
-    if (!x || !y || total <= 0) return ou_fail(-1, "pad: bad args");
+    if (!x || !y || batch <= 0 || n_in <= 0 || n_out <= 0) return ou_fail(-1, "pad: bad args");
     hipLaunchKernelGGL(pad_kernel, dim3(blocks_for(total, 256)), dim3(256), 0,
                        (hipStream_t)stream, x, x_bstride, y, n_in, n_out, left, total);
     return ou_check_launch("pad");
@@ -579,10 +598,12 @@ extern "C" int ou_signal_median(const float* x, float* y, int ensemble, int batc
 
 extern "C" int ou_snake_aa(const ou_snake_desc* d, void* stream)
 {
-    if (!d || !d->h || !d->out || !d->alpha || !d->k_up || !d->k_down || d->length <= 0)
+    if (!d || !d->h || !d->out || !d->alpha || !d->k_up || !d->k_down || d->length <= 0 || d->channels <= 0 ||
+        d->batch <= 0)
         return ou_fail(-1, "snake_aa: invalid descriptor");
-    if (d->taps_up > 32 || d->taps_down > 64)
-        return ou_fail(-1, "snake_aa: kernel too long");
+    if (d->taps_up <= 0 || d->taps_down <= 0) return ou_fail(-1, "snake_aa: empty filter");
+    if (d->taps_up > kSnakeMaxUp || d->taps_down > kSnakeMaxDown)
+        return ou_fail(-1, "snake_aa: kernel too long (taps_up <= %d, taps_down <= %d)", kSnakeMaxUp, kSnakeMaxDown);
     dim3 grid(blocks_for(d->length, kSnakeTile), d->channels, d->batch);
     hipLaunchKernelGGL(snake_aa_kernel, grid, dim3(256), 0, (hipStream_t)stream, *d);
     return ou_check_launch("snake_aa");

@@ -94,6 +94,7 @@ inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { std::m
 inline bool __any(bool p) { return p; }
 inline bool __all(bool p) { return p; }
 inline int atomicOr(int* p, int v) { const int o = *p; *p |= v; return o; }
+inline int atomicAdd(int* p, int v) { const int o = *p; *p += v; return o; }
 inline unsigned atomicMax(unsigned* p, unsigned v) { const unsigned o = *p; *p = o > v ? o : v; return o; }
 inline float __shfl_xor(float v, int) { return v; }
 

@@ -102,6 +102,39 @@ def test_emulator_catches_an_unclamped_block_read(tmp_path):
     _must_fail([exe])
 
 
+def test_misc_kernels_in_bounds(tmp_path):
+    """Every op of ou_misc.hip over the case tables of tests/test_gpu_misc.py
+    (exact-size buffers, strided inputs that end with the last item's window),
+    ou_embed and ou_snake_aa also at the largest sizes their entry points
+    accept; then every entry point refuses null pointers, non-positive sizes
+    and the sizes one past its limits (n_rff 129, dim 1025, taps 33 / 65)."""
+    exe = str(tmp_path / "misc_emu")
+    _build("misc_emu.cpp", exe, *ASAN)
+    out = _run([exe], env={"OUHIP_EMU_BLOCKS": "0"})   # every workgroup
+    assert "ok:" in out and " 0 descriptors refused" not in out
+
+
+def test_emulator_catches_the_old_embed_bound(tmp_path):
+    """ou_embed used to accept any n_rff <= 512, but embed_g_kernel's LDS
+    buffers hold the 8 n_rff wide layer only up to n_rff = 128.  With that
+    check restored (and the program's own refusal checks compiled out) the
+    emulator must report the LDS write at n_rff = 129."""
+    src = _mutant(tmp_path, "ou_misc.hip", "d->n_rff > kEmbedMax / 8 ||", "d->n_rff * 2 > 1024 ||")
+    exe = str(tmp_path / "misc_emu_rev")
+    _build("misc_emu.cpp", exe, *ASAN, f'-DOU_EMU_MISC_SRC="{src}"', "-DOU_EMU_MISC_OVER")
+    _must_fail([exe, "embed"], env={"OUHIP_EMU_BLOCKS": "0"})
+
+
+def test_emulator_catches_the_old_snake_staging_array(tmp_path):
+    """ou_snake_aa accepts 32 up / 64 down taps, which stage 321 input
+    samples per tile; the staging array used to hold 320.  With the old size
+    restored the run at the accepted limits must be reported."""
+    src = _mutant(tmp_path, "ou_misc.hip", "__shared__ float sh[kSnakeNs];", "__shared__ float sh[kSnakeTile + 64];")
+    exe = str(tmp_path / "misc_emu_rev")
+    _build("misc_emu.cpp", exe, *ASAN, f'-DOU_EMU_MISC_SRC="{src}"')
+    _must_fail([exe], env={"OUHIP_EMU_BLOCKS": "0"})
+
+
 def test_recorded_plan_convs_in_bounds(tmp_path):
     """Every conv descriptor of a recorded enhance program (small-channel
     UNIVERSE++ config, batch 2), every tile shape x tiles-per-workgroup."""
