@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define OUHIP_ABI_VERSION 9
+#define OUHIP_ABI_VERSION 10
 
 int ou_abi_version(void);
 const char* ou_last_error(void);
@@ -729,6 +729,78 @@ int ou_model_enhance(ou_model* m, const float* mix, float* out, uint64_t seed, u
 int ou_model_status(ou_model* m);
 int ou_model_info(const ou_model* m, ou_bundle_meta* meta);
 void ou_model_destroy(ou_model* m);
+
+/* ------------------------------------------------------------------------
+ * Windowed enhance of a long clip (ou_long.hip; DESIGN.md section 14 has the
+ * definition, open_universe_amd/longform.py restates it on the host).
+ *
+ * A clip of T samples is cut into n windows of `window` (W) samples that
+ * overlap by `overlap` (O) samples, 0 <= O <= W / 2, hop H = W - O:
+ *   n = 1 if T == W, else 1 + ceil((T - W) / H);  start(i) = min(i H, T - W)
+ * (the last window is shifted back to end at T; nothing is padded), an index
+ * i >= n meaning window n - 1.  Window i >= 1 fades in over the O samples
+ * [e(i-1) - O, e(i-1)), e(i) = start(i) + W, with weight
+ *   f(u) = sin^2(pi (2 u + 1) / (4 O)),  u = t - (e(i-1) - O)
+ * while window i - 1 fades out with 1 - f(u); window i has weight 0 before
+ * its fade-in, 1 after it until window i + 1 fades in (O = 0: a hard switch
+ * at e(i-1)).  At most two windows are non-zero at a sample and the weights
+ * sum to 1 on [0, T).  T < W is refused everywhere: such a clip is one plain
+ * enhance.
+ *
+ * ou_long_windows: the arithmetic alone (host; no HIP call): *n and the
+ * start of the last window.
+ *
+ * ou_window_gather: y[r][b][j] = x[r][start(first + b) + j], j < win, for
+ * `rows` source rows x_rstride apart and b < count (<= 65535), first < n.
+ * win = W for the clip; the sampler's noise uses win = the padded window
+ * length, its rows holding start(n - 1) + win values.  x rows must hold
+ * T - W + win values; y item b of row r starts at r y_rstride + b y_bstride.
+ *
+ * ou_overlap_add: adds those of windows [first, first + count) below n (window
+ * first + b at w + b w_bstride, W values each), weighted as above, into
+ * y[0, T).  fade: [2][O] floats, f(u) then 1 - f(u), rounded from float64
+ * (ou_long_fade fills a host array; NULL when O = 0).  The call with
+ * first = 0 writes every sample of y (0 where none of its windows is
+ * non-zero); a later call adds to what is there.  Products and sums are
+ * rounded one by one, so calling it window by window in order, or once, or
+ * in any grouping, stores the same bits.
+ *
+ * All three refuse null pointers, non-positive sizes, O > W / 2, T < W,
+ * first < 0 and first >= n.
+ * ---------------------------------------------------------------------- */
+int ou_long_windows(int64_t T, int window, int overlap, int64_t* n, int64_t* last_start);
+int ou_long_fade(int overlap, float* fade /* host, [2][overlap] */);
+int ou_window_gather(const float* x, int64_t x_rstride, int rows, int64_t T, int window, int overlap,
+                     int64_t first, int count, int64_t win, float* y, int64_t y_rstride, int64_t y_bstride,
+                     void* stream);
+int ou_overlap_add(const float* w, int64_t w_bstride, int64_t T, int window, int overlap, int64_t first,
+                   int count, const float* fade, float* y, void* stream);
+
+/* Windowed enhance through a loaded bundle: W and the group size B are the
+ * bundle's own (mix.length, mix.batch); x and out are device pointers of n
+ * floats, n > W (n <= W is ou_model_enhance's case and refused).  Windows
+ * [g B, g B + B) run as one replay each, g = 0, 1, ...: the two kernels
+ * above gather the group's windows and noise into the bundle's buffers and
+ * overlap-add its output into out, all on ``stream``; unused slots of the
+ * last group repeat the last window.  The noise is global: `count` draws
+ * (noise.count) of L = start(n - 1) + noise.length values, window i of draw
+ * k using noise[k L + start(i) ...), so overlapping windows see the same
+ * noise.  ou_model_long_noise returns count L (the floats of that buffer)
+ * and, if len is not NULL, L.
+ *   _noise: the caller provides the draws, [count][L].
+ *   ou_model_enhance_long: draws them with ou_randn into ``workspace``
+ *   (caller-owned device memory of ou_model_long_noise floats, free for
+ *   reuse when the stream has passed the call): draw k is the stream at
+ *   (seed, counter offset + k ceil(L / 4)).
+ * Nothing is allocated after load.  The fade table lives in the model and is
+ * uploaded when `overlap` differs from the previous call's (that upload
+ * waits for the previous call's stream).  ou_model_status is checked once,
+ * after the last group, as after ou_model_enhance.                          */
+int64_t ou_model_long_noise(const ou_model* m, int64_t n, int overlap, int64_t* len);
+int ou_model_enhance_long_noise(ou_model* m, const float* x, int64_t n, int overlap, const float* noise,
+                                float* out, void* stream);
+int ou_model_enhance_long(ou_model* m, const float* x, int64_t n, int overlap, float* out, uint64_t seed,
+                          uint64_t offset, float* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ from ctypes import POINTER, c_char, c_char_p, c_float, c_int, c_int32, c_int64, 
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OUHIP_LIB", os.path.join(_HERE, "libouhip.so"))
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 fp = c_void_p  # device pointers are passed as integers
 
@@ -245,6 +245,14 @@ EXPORTS = {
     "ou_model_status": (c_int, [c_void_p]),
     "ou_model_info": (c_int, [c_void_p, POINTER(BundleMeta)]),
     "ou_model_destroy": (None, [c_void_p]),
+    "ou_long_windows": (c_int, [c_int64, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "ou_long_fade": (c_int, [c_int, POINTER(c_float)]),
+    "ou_window_gather": (c_int, [fp, c_int64, c_int, c_int64, c_int, c_int, c_int64, c_int, c_int64, fp, c_int64,
+                                 c_int64, c_void_p]),
+    "ou_overlap_add": (c_int, [fp, c_int64, c_int64, c_int, c_int, c_int64, c_int, fp, fp, c_void_p]),
+    "ou_model_long_noise": (c_int64, [c_void_p, c_int64, c_int, POINTER(c_int64)]),
+    "ou_model_enhance_long_noise": (c_int, [c_void_p, fp, c_int64, c_int, fp, fp, c_void_p]),
+    "ou_model_enhance_long": (c_int, [c_void_p, fp, c_int64, c_int, fp, c_uint64, c_uint64, fp, c_void_p]),
 }
 
 _lib = None

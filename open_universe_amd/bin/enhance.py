@@ -9,7 +9,10 @@ Differences: audio is resampled to ``model.fs`` and back on the GPU
 (``audio.resample``); WAV and FLAC are read (FLAC by the native decoder,
 ``audio.load_flac``), mp3 is not; the model must be a local checkpoint
 (the Hugging Face hub needs the network).  Files are enhanced in groups of
-``--chunk`` with ``--streams`` clips in flight (Universe.enhance_many).  Under
+``--chunk`` with ``--streams`` clips in flight (Universe.enhance_many); with
+``--window SECONDS`` (and ``--overlap``, ``--window-batch``) a file longer than
+the window goes through ``Universe.enhance_long`` instead, so that every long
+file uses one plan shape whatever its length.  Under
 torchrun (WORLD_SIZE > 1) each rank enhances its share of the files on
 ``cuda:LOCAL_RANK`` (``sharding.shard_utterances``, balanced by file size) --
 no collectives.
@@ -46,7 +49,9 @@ def find_files(path):
     return [p for p in path.rglob("*") if p.suffix in AUDIO_SUFFIXES], path, True
 
 
-def main(argv=None):
+def build_parser():
+    """The CLI's own options (the ``enhance()`` options are added from the
+    loaded model's signature in :func:`main`)."""
     parser = argparse.ArgumentParser(description="Enhance a file or a directory of audio files")
     parser.add_argument("input", type=Path, help="Path to an audio file or a folder of audio files")
     parser.add_argument("output", type=Path, help="Output path; for a folder the structure is retained")
@@ -58,6 +63,32 @@ def main(argv=None):
                         help="clips in flight at once on separate HIP streams (Universe.enhance_many); 1 = one "
                              "enhance() per file, as the reference")
     parser.add_argument("--chunk", type=int, default=8, help="files read, enhanced and written per group")
+    parser.add_argument("--window", type=float, default=None, metavar="SECONDS",
+                        help="files longer than this go through Universe.enhance_long in windows of this length "
+                             "(default: off, every file is one enhance)")
+    parser.add_argument("--overlap", type=float, default=0.5, metavar="SECONDS",
+                        help="crossfaded overlap of two windows, at most half the window (with --window)")
+    parser.add_argument("--window-batch", type=int, default=8, metavar="N",
+                        help="windows per replay (with --window)")
+    return parser
+
+
+def window_settings(args, fs):
+    """(window, overlap) in samples at ``fs`` from --window / --overlap, or
+    None when --window is off."""
+    if args.window is None:
+        return None
+    W, O = int(round(args.window * fs)), int(round(args.overlap * fs))
+    if W < 1 or O < 0 or O > W // 2:
+        raise SystemExit(f"--window {args.window} --overlap {args.overlap}: the window must be positive and the "
+                         "overlap between 0 and half the window")
+    if args.window_batch < 1:
+        raise SystemExit(f"--window-batch {args.window_batch}: at least 1")
+    return W, O
+
+
+def main(argv=None):
+    parser = build_parser()
     args, _ = parser.parse_known_args(argv)
 
     rank, local, world = dist_env()
@@ -90,6 +121,20 @@ def main(argv=None):
     noise_kw = {k: enhance_kwargs.get(k) for k in ("n_steps", "target", "use_aux_signal", "ensemble",
                                                   "warm_start")}
 
+    win = window_settings(args, model.fs)
+    long_kw = {}
+    if win is not None:
+        for k in ("target", "fake_score_snr", "use_aux_signal", "ensemble", "warm_start"):
+            if enhance_kwargs.get(k) not in (None, False):
+                raise SystemExit(f"--window does not support --{k}")
+        # the window settings ride along: a skipped long file draws what enhance_long draws
+        noise_kw.update(window=win[0], overlap=win[1])
+        long_kw = dict({k: enhance_kwargs.get(k) for k in ("n_steps", "epsilon", "keep_rms", "rng")},
+                       window=win[0], overlap=win[1], batch=args.window_batch)
+
+    def is_long(x):
+        return win is not None and x.shape[-1] > win[0]
+
     def skip(paths):
         for p in paths:
             ch, n, fs = audio_info(p)
@@ -114,14 +159,23 @@ def main(argv=None):
         loaded = [load_audio(p) for p in group]
         with torch.no_grad():
             xs = [resample(a.to(device), fs, model.fs) for a, fs in loaded]
-            if many_ok:
-                ys = model.enhance_many(xs, streams=args.streams, pre_noise=lambda j: skip(skip_before[i + j]),
-                                        **many_kw)
-            else:
-                ys = []
-                for j, x in enumerate(xs):
+            # in file order (the noise order): a long file on its own through
+            # enhance_long, every run of other files the existing way
+            ys, j = [None] * len(xs), 0
+            while j < len(xs):
+                k = j + 1
+                if is_long(xs[j]):
                     skip(skip_before[i + j])
-                    ys.append(model.enhance(x, **enhance_kwargs))
+                    ys[j] = model.enhance_long(xs[j], **long_kw)
+                elif many_ok:
+                    while k < len(xs) and not is_long(xs[k]):
+                        k += 1
+                    ys[j:k] = model.enhance_many(xs[j:k], streams=args.streams,
+                                                 pre_noise=lambda q, j=j: skip(skip_before[i + j + q]), **many_kw)
+                else:
+                    skip(skip_before[i + j])
+                    ys[j] = model.enhance(xs[j], **enhance_kwargs)
+                j = k
             ys = [resample(y, model.fs, fs) for y, (_, fs) in zip(ys, loaded)]
         for path, y, (_, fs) in zip(group, ys, loaded):
             out = out_path(path)

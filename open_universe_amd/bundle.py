@@ -355,6 +355,50 @@ class Bundle:
                 "model_enhance")
         return out
 
+    def long_noise(self, n, overlap):
+        """(floats of the global noise buffer, L) of a windowed enhance of an
+        ``n``-sample clip: ``n_noise`` draws of ``L`` values (longform.py)."""
+        ln = ctypes.c_int64(0)
+        total = self.lib.ou_model_long_noise(self.h, int(n), int(overlap), ctypes.byref(ln))
+        if total < 0:
+            L.check(int(total), "model_long_noise")
+        return int(total), int(ln.value)
+
+    def _long(self, x):
+        import torch
+
+        if not x.is_cuda or x.dtype != torch.float32 or x.ndim != 1:
+            raise ValueError("x must be a one-dimensional float32 HIP tensor")
+        x = x.contiguous()
+        return x, torch.empty_like(x), c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+
+    def enhance_long_with_noise(self, x, overlap, noise):
+        """Windowed enhance (longform.py) of one clip ``x`` of more than
+        ``length`` samples: windows of the bundle's ``length``, ``overlap``
+        samples crossfaded, groups of the bundle's ``batch`` windows per
+        replay, on the caller's global noise of n_noise x L values
+        (``long_noise``).  Returns (n,); call status() before using it."""
+        x, out, stream = self._long(x)
+        total, _ = self.long_noise(x.numel(), overlap)
+        if not noise.is_cuda or noise.dtype != x.dtype or noise.numel() != total:
+            raise ValueError(f"noise must be a float32 HIP tensor of {total} values")
+        noise = noise.contiguous()
+        L.check(self.lib.ou_model_enhance_long_noise(self.h, x.data_ptr(), x.numel(), int(overlap), noise.data_ptr(),
+                                                     out.data_ptr(), stream), "model_enhance_long_noise")
+        return out
+
+    def enhance_long(self, x, overlap, seed=0, offset=0):
+        """The same on the native noise stream: draw k is ou_randn at
+        (seed, counter offset + k ceil(L / 4))."""
+        import torch
+
+        x, out, stream = self._long(x)
+        total, _ = self.long_noise(x.numel(), overlap)
+        ws = torch.empty(total, dtype=torch.float32, device=x.device)
+        L.check(self.lib.ou_model_enhance_long(self.h, x.data_ptr(), x.numel(), int(overlap), out.data_ptr(),
+                                               int(seed), int(offset), ws.data_ptr(), stream), "model_enhance_long")
+        return out
+
     def status(self):
         """Wait for the latest enhance and read the status words: 0 when it
         ran clean; raises OuHipError on a GRU hand-off timeout and

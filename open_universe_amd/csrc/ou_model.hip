@@ -23,6 +23,11 @@ struct ou_model {
     int32_t* status = nullptr;
     std::vector<int32_t> status_host;
     hipStream_t last = nullptr;   // the stream of the latest enhance: ou_model_status waits for it
+    // windowed enhance (ou_model_enhance_long*): the crossfade table [2][overlap] for the
+    // overlap of the latest call, in a buffer of mix.length floats allocated at load
+    float* fade = nullptr;
+    int fade_overlap = -1;
+    std::vector<float> fade_host;
 };
 
 namespace {
@@ -64,6 +69,7 @@ int build(ou_model* m, const char* path, int capture)
     m->out = (float*)io_ptr(m, m->meta.out);
     m->status = (int32_t*)io_ptr(m, m->meta.status);
     m->status_host.assign(m->meta.status.count, 0);
+    OU_HIP_CHECK(hipMalloc((void**)&m->fade, 4ull * (size_t)m->meta.mix.length), "bundle_load: fade table");
     OU_HIP_CHECK(hipDeviceSynchronize(), "bundle_load: sync");   // the uploads and fills, before any stream uses them
     if (capture) {
         if ((rc = ou_program_capture(m->prog))) return rc;
@@ -94,6 +100,57 @@ int64_t noise_count(const ou_model* m)
     return (int64_t)m->meta.noise.count * m->meta.noise.batch * m->meta.noise.length;
 }
 
+// the windowed enhance's geometry for a clip of n samples: the window count
+// and L, the length of one global noise draw
+int long_check(const ou_model* m, const char* what, int64_t n, int overlap, int64_t* n_win, int64_t* len)
+{
+    const int W = m->meta.mix.length;
+    if (n <= W) return ou_fail(-1, "%s: a clip of %lld samples fits one window of %d: use ou_model_enhance", what,
+                               (long long)n, W);
+    int64_t last = 0;
+    const int rc = ou_long_windows(n, W, overlap, n_win, &last);
+    if (rc) return rc;
+    *len = last + m->meta.noise.length;
+    return 0;
+}
+
+int long_fade(ou_model* m, int overlap, hipStream_t s)
+{
+    if (overlap == m->fade_overlap) return 0;
+    // the previous call's overlap-adds may still read the table
+    OU_HIP_CHECK(hipStreamSynchronize(m->last), "model_enhance_long: sync");
+    if (s != m->last) OU_HIP_CHECK(hipStreamSynchronize(s), "model_enhance_long: sync");
+    m->fade_host.assign(2 * (size_t)overlap + 1, 0.f);
+    const int rc = ou_long_fade(overlap, m->fade_host.data());
+    if (rc) return rc;
+    if (overlap > 0)
+        OU_HIP_CHECK(hipMemcpy(m->fade, m->fade_host.data(), 8ull * overlap, hipMemcpyHostToDevice),
+                     "model_enhance_long: fade table");
+    m->fade_overlap = overlap;
+    return 0;
+}
+
+// groups of `batch` windows: gather, replay, overlap-add, all on s
+int long_run(ou_model* m, const float* x, int64_t n, int overlap, const float* noise, int64_t n_win, int64_t len,
+             float* out, hipStream_t s)
+{
+    const int W = m->meta.mix.length, B = m->meta.mix.batch, Tp = m->meta.noise.length;
+    int rc = long_fade(m, overlap, s);
+    if (rc) return rc;
+    m->last = s;
+    for (int64_t first = 0; first < n_win; first += B) {
+        if ((rc = ou_window_gather(x, 0, 1, n, W, overlap, first, B, W, m->mix, 0, W, s))) return rc;
+        if (m->meta.noise.count > 0 &&
+            (rc = ou_window_gather(noise, len, m->meta.noise.count, n, W, overlap, first, B, Tp, m->noise,
+                                   (int64_t)B * Tp, Tp, s)))
+            return rc;
+        if ((rc = m->captured ? ou_program_launch(m->prog, s) : ou_program_run(m->prog, s))) return rc;
+        if ((rc = ou_overlap_add(m->out, W, n, W, overlap, first, B, overlap > 0 ? m->fade : nullptr, out, s)))
+            return rc;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -105,6 +162,7 @@ void ou_model_destroy(ou_model* m)
     if (m->prog) ou_program_destroy(m->prog);
     for (void* p : m->regions)
         if (p) (void)hipFree(p);
+    if (m->fade) (void)hipFree(m->fade);
     if (m->bundle) ou_bundle_close(m->bundle);
     delete m;
 }
@@ -142,6 +200,39 @@ int ou_model_enhance(ou_model* m, const float* mix, float* out, uint64_t seed, u
     if (rc) return rc;
     if ((rc = ou_randn(m->noise, noise_count(m), seed, offset, stream))) return rc;
     return replay(m, out, s);
+}
+
+int64_t ou_model_long_noise(const ou_model* m, int64_t n, int overlap, int64_t* len)
+{
+    if (!m) return ou_fail(-1, "model_long_noise: null");
+    int64_t n_win = 0, l = 0;
+    const int rc = long_check(m, "model_long_noise", n, overlap, &n_win, &l);
+    if (rc) return rc;
+    if (len) *len = l;
+    return (int64_t)m->meta.noise.count * l;
+}
+
+int ou_model_enhance_long_noise(ou_model* m, const float* x, int64_t n, int overlap, const float* noise,
+                                float* out, void* stream)
+{
+    if (!m || !x || !noise || !out) return ou_fail(-1, "model_enhance_long_noise: null");
+    int64_t n_win = 0, len = 0;
+    const int rc = long_check(m, "model_enhance_long_noise", n, overlap, &n_win, &len);
+    if (rc) return rc;
+    return long_run(m, x, n, overlap, noise, n_win, len, out, (hipStream_t)stream);
+}
+
+int ou_model_enhance_long(ou_model* m, const float* x, int64_t n, int overlap, float* out, uint64_t seed,
+                          uint64_t offset, float* workspace, void* stream)
+{
+    if (!m || !x || !out || !workspace) return ou_fail(-1, "model_enhance_long: null");
+    int64_t n_win = 0, len = 0;
+    int rc = long_check(m, "model_enhance_long", n, overlap, &n_win, &len);
+    if (rc) return rc;
+    const uint64_t per_draw = (uint64_t)((len + 3) / 4);
+    for (int k = 0; k < m->meta.noise.count; ++k)
+        if ((rc = ou_randn(workspace + (int64_t)k * len, len, seed, offset + (uint64_t)k * per_draw, stream))) return rc;
+    return long_run(m, x, n, overlap, workspace, n_win, len, out, (hipStream_t)stream);
 }
 
 int ou_model_status(ou_model* m)

@@ -1,0 +1,123 @@
+"""Windowed enhance of a long clip: the definition.
+
+Pure Python and numpy; imports without a GPU.  ``Universe.enhance_long``, the
+CLI, ``bundle.Bundle.enhance_long`` and the C host (csrc/ou_long.hip,
+ou_model_enhance_long) all compute what this module states.
+
+Symbols: ``W`` the window and ``O`` the overlap in samples at ``model.fs``,
+``0 <= O <= W / 2``; ``H = W - O`` the hop; ``T`` the clip length.
+
+Windows.  ``n = 1`` if ``T <= W`` else ``1 + ceil((T - W) / H)``;
+``start_i = min(i H, T - W)`` -- the last window is shifted back to end at
+``T``, nothing is zero-padded (per-item normalisation would see a quieter
+window); ``e_i = start_i + W``.  An index ``i >= n`` means window ``n - 1``:
+the unused batch slots of the last group repeat the last real window, whose
+content is safe and whose outputs are dropped.
+
+Seams.  Window ``i >= 1`` fades in over the global samples
+``[e_{i-1} - O, e_{i-1})`` with weight ``f(u) = sin^2(pi (2 u + 1) / (4 O))``
+at ``u = t - (e_{i-1} - O)``; window ``i - 1`` has ``1 - f(u)`` there.  Window
+``i`` has weight 0 before its fade-in (the head of the shifted last window is
+discarded), 0 outside its span and 1 elsewhere inside it; ``O = 0`` is a hard
+switch at ``e_{i-1}``.  With ``O <= W / 2`` at most two windows are non-zero
+at a sample, and the weights sum to 1 on ``[0, T)``.
+
+Noise.  One global stream per sampler draw: draw ``k`` has the shape
+``(1, 1, L)``, ``L = start_{n-1} + Tp`` with ``Tp`` the plan's padded window
+length, drawn in the sampler's order (x0, then one z per intermediate step);
+window ``i`` uses ``G[k, 0, start_i : start_i + Tp]``.  Two windows see the
+same noise wherever they overlap, and the draws do not depend on how the
+windows are grouped into batches.
+
+Result.  ``y[t] = sum_i weight_i(t) out_i[t - start_i]`` with ``out_i`` what
+``enhance()`` returns for window ``i`` inside its batch-``B`` group
+(windows ``[g B, g B + B)``, ``B = min(batch, n)``) on its slice of the noise,
+through the normal finish (crop, ``keep_rms`` against the window's own input
+RMS, peak division).
+"""
+import numpy as np
+
+
+def check(T, W, O):
+    """Validate (T, W, O); returns them as ints."""
+    T, W, O = int(T), int(W), int(O)
+    if W < 1:
+        raise ValueError(f"window must be at least one sample, got {W}")
+    if O < 0 or O > W // 2:
+        raise ValueError(f"overlap must lie in [0, window / 2] = [0, {W // 2}], got {O}")
+    if T < 1:
+        raise ValueError(f"the clip has {T} samples")
+    return T, W, O
+
+
+def n_windows(T, W, O):
+    T, W, O = check(T, W, O)
+    if T <= W:
+        return 1
+    H = W - O
+    return 1 + -(-(T - W) // H)
+
+
+def start(i, T, W, O):
+    """Start of window ``i``; ``i >= n`` clamps to the last window."""
+    T, W, O = check(T, W, O)
+    i = min(int(i), n_windows(T, W, O) - 1)
+    return max(0, min(i * (W - O), T - W))
+
+
+def starts(T, W, O):
+    return [start(i, T, W, O) for i in range(n_windows(T, W, O))]
+
+
+def noise_len(T, W, O, Tp):
+    """``L``: the length of one global noise draw."""
+    return start(n_windows(T, W, O) - 1, T, W, O) + int(Tp)
+
+
+def groups(T, W, O, batch):
+    """(B, [first window of each group]): ``B = min(batch, n)``."""
+    n = n_windows(T, W, O)
+    B = max(1, min(int(batch), n))
+    return B, list(range(0, n, B))
+
+
+def fade(O):
+    """float64 ``f(u)``, ``u = 0 .. O - 1``."""
+    u = np.arange(int(O), dtype=np.float64)
+    return np.sin(np.pi * (2.0 * u + 1.0) / (4.0 * O)) ** 2 if O else u
+
+
+def fade_table(O):
+    """The table the kernels read: float32 (2, O), ``f`` then ``1 - f``, each
+    rounded once from float64 (so their sum is within one float32 ulp of 1)."""
+    f = fade(O)
+    return np.stack([f, 1.0 - f]).astype(np.float32)
+
+
+def weights(T, W, O, dtype=np.float64):
+    """(n, T) weights: row ``i`` is window ``i``'s weight at every sample of
+    the clip.  ``dtype=float32`` gives the weights the kernels use."""
+    T, W, O = check(T, W, O)
+    st = starts(T, W, O)
+    n = len(st)
+    tab = fade_table(O).astype(np.float64) if dtype == np.float32 else np.stack([fade(O), 1.0 - fade(O)])
+    w = np.zeros((n, T), dtype=np.float64)
+    for i, s in enumerate(st):
+        lo = 0 if i == 0 else st[i - 1] + W - O          # where window i fades in
+        hi = min(T, s + W) if i == n - 1 else s + W - O   # where window i + 1 fades in
+        w[i, lo:hi] = 1.0
+        if i:
+            w[i, lo:lo + O] = tab[0]
+            w[i - 1, lo:lo + O] = tab[1]
+    return w.astype(dtype)
+
+
+def overlap_add(outs, T, W, O, dtype=np.float64):
+    """``y[t] = sum_i weight_i(t) outs[i][t - start_i]`` for outs (n, W)."""
+    outs = np.asarray(outs)
+    w = weights(T, W, O, dtype=np.float32 if dtype == np.float32 else np.float64)
+    y = np.zeros(int(T), dtype=dtype)
+    for i, s in enumerate(starts(T, W, O)):
+        m = min(W, int(T) - s)
+        y[s:s + m] += (w[i, s:s + m].astype(dtype) * outs[i, :m].astype(dtype)).astype(dtype)
+    return y

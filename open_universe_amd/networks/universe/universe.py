@@ -17,6 +17,7 @@ with ``torch.randn(..., generator=rng)`` on the device in the reference's order
 reference on the same device and generator.
 """
 import collections
+import ctypes
 import itertools
 import math
 import os
@@ -85,6 +86,7 @@ class Universe(nn.Module):
         self._engine = None
         self._plans = collections.OrderedDict()   # LRU of recorded plans, see _plan()
         self._inflight = set()   # plan keys submitted by enhance_many and not yet checked
+        self._fades = {}         # (overlap, device) -> enhance_long's crossfade table on the device
         self._conv_prec = None   # None: OUHIP_CONV_PREC; 0 after a range error no exponent widening fixed
         self.range_fallbacks = 0   # enhance()/enhance_many() calls rerun with f32 operands
         self.range_widenings = 0   # reruns after widening the staging exponents of named layers
@@ -220,13 +222,16 @@ class Universe(nn.Module):
 
     # ------------------------------------------------------------------ noise
     def noise_shapes(self, mix_shape, n_steps: Optional[int] = None, target=None, use_aux_signal=False,
-                     ensemble=None, warm_start=None, **_):
+                     ensemble=None, warm_start=None, window=None, overlap=None, **_):
         """The shapes of the ``torch.randn(..., generator=rng)`` draws one
         ``enhance(mix, ...)`` makes, in draw order (universe.py:39-41,322-343:
         x0, then one z per intermediate step; the known-answer mode also draws
         the score noise of every step, :278-298).  Drawing and discarding
         these advances ``rng`` exactly as that enhance would (bin/enhance.py
-        keeps a multi-rank run's noise assignment equal to the 1-rank run's)."""
+        keeps a multi-rank run's noise assignment equal to the 1-rank run's).
+        With ``window`` (and ``overlap``, in samples) the shapes are those of
+        ``enhance_long(mix, window, overlap, ...)``: for a clip longer than the
+        window its global draws (1, 1, L), clip by clip (longform.py)."""
         if n_steps is None:
             n_steps = self.diff_kwargs.n_steps
         shape = tuple(mix_shape)
@@ -234,6 +239,17 @@ class Universe(nn.Module):
             shape = (1, 1) + shape
         elif len(shape) == 2:
             shape = (shape[0], 1, shape[1])
+        if window is not None and shape[-1] > int(window):
+            from ... import longform
+
+            for k, v in (("target", target), ("use_aux_signal", use_aux_signal), ("ensemble", ensemble),
+                         ("warm_start", warm_start)):
+                if v is not None and v is not False:
+                    raise NotImplementedError(f"enhance_long does not support {k}")
+            W = int(window)
+            Wp = W + self.tot_ds - W % self.tot_ds
+            Ln = longform.noise_len(shape[-1], W, int(overlap or 0), Wp)
+            return [(1, 1, Ln)] * int(n_steps) * shape[0]
         B, T = shape[0] * (ensemble or 1), shape[-1]
         Tp = T + self.tot_ds - T % self.tot_ds
         if target is not None:
@@ -267,8 +283,6 @@ class Universe(nn.Module):
         warm_start: Optional[int] = None,
     ) -> torch.Tensor:
         """Reverse-diffusion enhancement (universe.py:231-375)."""
-        from ...plan import EnhancePlan
-
         if epsilon is None:
             epsilon = self.diff_kwargs.epsilon
         if n_steps is None:
@@ -294,14 +308,8 @@ class Universe(nn.Module):
             B, _, T = mix.shape
             # mean / median / signal_median reduce on the device inside the plan
             ens_mode = {"mean": 0, "median": 1, "signal_median": 2}[ensemble_stat] if ensemble is not None else None
-            key = (B, T, int(n_steps), float(epsilon), bool(keep_rms), bool(use_aux_signal),
-                   warm_start, ensemble, ens_mode)
-            def make_plan(arena):
-                return EnhancePlan(self._get_engine(), B, T, int(n_steps), float(epsilon), keep_rms=bool(keep_rms),
-                                   use_aux_signal=bool(use_aux_signal), warm_start=warm_start,
-                                   diff=dict(self.diff_kwargs), ensemble=ensemble,
-                                   ensemble_mode=ens_mode, arena=arena)
-
+            key, make_plan = self._plan_spec(B, T, n_steps, epsilon, keep_rms, use_aux_signal, warm_start,
+                                             ensemble, ens_mode)
             plan = self._arena_plan(key, 0, make_plan)
             try:
                 x = plan(mix, rng, clone=True)[:, None, :]
@@ -320,6 +328,131 @@ class Universe(nn.Module):
         elif x_ndim == 2:
             x = x[:, 0, :]
         return x
+
+    def _plan_spec(self, B, T, n_steps, epsilon, keep_rms=False, use_aux_signal=False, warm_start=None,
+                   ensemble=None, ens_mode=None):
+        """(key in the plan LRU, ``make_plan(arena)``) of the EnhancePlan that
+        ``enhance`` runs for a (B, 1, T) input with these options
+        (``enhance_long`` takes its (batch, window) plan from here too)."""
+        from ...plan import EnhancePlan
+
+        key = (B, T, int(n_steps), float(epsilon), bool(keep_rms), bool(use_aux_signal),
+               warm_start, ensemble, ens_mode)
+
+        def make_plan(arena):
+            return EnhancePlan(self._get_engine(), B, T, int(n_steps), float(epsilon), keep_rms=bool(keep_rms),
+                               use_aux_signal=bool(use_aux_signal), warm_start=warm_start,
+                               diff=dict(self.diff_kwargs), ensemble=ensemble,
+                               ensemble_mode=ens_mode, arena=arena)
+
+        return key, make_plan
+
+    def _fade_table(self, overlap, dev):
+        """The crossfade table of ou_overlap_add on the device (cached)."""
+        from ... import longform
+
+        tabs = self._fades
+        key = (int(overlap), str(dev))
+        if key not in tabs:
+            if len(tabs) >= 8:
+                tabs.clear()
+            tabs[key] = torch.from_numpy(longform.fade_table(overlap)).to(dev) if overlap else None
+        return tabs[key]
+
+    def enhance_long(self, mix, window: int, overlap: int, batch: int = 8, n_steps: Optional[int] = None,
+                     epsilon: Optional[float] = None, rng: Optional[torch.Generator] = None,
+                     keep_rms: Optional[bool] = False, **unsupported) -> torch.Tensor:
+        """Windowed enhance of a long clip (opt-in; ``enhance`` is unchanged and
+        a clip still cannot be split without changing the result -- this entry
+        point has its own, precisely defined one: longform.py, DESIGN.md
+        section 14).  ``mix`` is (T,), (B, T) or (B, 1, T); ``window`` and
+        ``overlap`` are in samples at ``self.fs``, ``0 <= overlap <=
+        window / 2``.  The clip is cut into windows of ``window`` samples
+        ``window - overlap`` apart (the last one shifted back to end with the
+        clip); groups of ``min(batch, n)`` windows run through the plan
+        ``enhance`` would use for a (batch, window) input -- one plan shape for
+        every clip longer than the window, chains of one window's length -- on
+        slices of one global noise stream per sampler draw, and the outputs
+        are crossfaded over the overlaps (sin^2 weights that sum to 1).
+
+        For ``T <= window`` this is ``enhance(mix, ...)`` itself: the same
+        plan, the same draws, bit-equal.  Several clips run one after another,
+        their noise drawn in clip order.  ``target``, ``use_aux_signal``,
+        ``ensemble`` and ``warm_start`` are refused.
+
+        Device memory beyond the plan's arena: the clip (T floats), the output
+        (T floats) and the global noise, ``n_noise * L`` floats with
+        ``n_noise = n_steps`` draws of ``L = start_{n-1} + Tp`` (at most
+        ``T + tot_ds``) values -- per clip, ``(2 + n_steps) T`` floats."""
+        from ... import longform
+
+        for k, v in unsupported.items():
+            if k in ("target", "fake_score_snr", "use_aux_signal", "ensemble", "ensemble_stat", "warm_start"):
+                if v is not None and v is not False and not (k == "ensemble_stat" and v == "median"):
+                    raise NotImplementedError(f"enhance_long does not support {k}")
+            else:
+                raise TypeError(f"enhance_long() got an unexpected keyword argument {k!r}")
+        if mix.ndim > 3 or mix.ndim < 1 or (mix.ndim == 3 and mix.shape[1] != 1):
+            raise ValueError("The input should be (T,), (B, T) or (B, 1, T)")
+        T = mix.shape[-1]
+        T, W, O = longform.check(T, window, overlap)   # before anything is launched
+        if int(batch) < 1:
+            raise ValueError(f"batch must be at least 1, got {batch}")
+        if T <= W:
+            return self.enhance(mix, n_steps=n_steps, epsilon=epsilon, rng=rng, keep_rms=keep_rms)
+        if epsilon is None:
+            epsilon = self.diff_kwargs.epsilon
+        if n_steps is None:
+            n_steps = self.diff_kwargs.n_steps
+        eng = self._get_engine()
+        dev = eng.device
+        # on the engine's device, as enhance() copies its input there: the kernels read the clip in place
+        clips = mix.reshape(-1, T).to(device=dev, dtype=torch.float32).contiguous()
+        B, firsts = longform.groups(T, W, O, batch)
+        n_noise = int(n_steps)
+        Ln = longform.noise_len(T, W, O, W + self.tot_ds - W % self.tot_ds)
+        lib = L.load()
+        fade = self._fade_table(O, dev)
+        fade_ptr = fade.data_ptr() if fade is not None else 0
+
+        def run(x, G):
+            # the plan, under the key in the plan LRU, of enhance() on a (B, W) batch
+            key, make_plan = self._plan_spec(B, W, n_steps, epsilon, keep_rms)
+            plan = self._arena_plan(key, 0, make_plan)
+            if plan.n_noise != n_noise or plan.Tp + longform.start(len(firsts) * B, T, W, O) != Ln:
+                raise L.OuHipError(f"enhance_long: the plan draws {plan.n_noise} x {plan.Tp}, expected {n_noise} "
+                                   f"draws and a global length of {Ln}")
+            y = torch.empty(T, dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            sp = ctypes.c_void_p(stream)
+            for first in firsts:
+                L.check(lib.ou_window_gather(x.data_ptr(), 0, 1, T, W, O, first, B, W, plan.MIX.data_ptr(), 0, W, sp),
+                        "window_gather")
+                L.check(lib.ou_window_gather(G.data_ptr(), Ln, n_noise, T, W, O, first, B, plan.Tp,
+                                             plan.NZ.data_ptr(), B * plan.Tp, plan.Tp, sp), "window_gather")
+                plan._launch(stream, True)
+                L.check(lib.ou_overlap_add(plan.OUT.data_ptr(), W, T, W, O, first, B, fade_ptr, y.data_ptr(), sp),
+                        "overlap_add")
+            plan.check(pinned=True)   # once, after the last group
+            return y
+
+        outs = []
+        for x in clips:
+            G = torch.empty((n_noise, 1, 1, Ln), dtype=torch.float32, device=dev)
+            for k in range(n_noise):   # the sampler's order: x0, then one z per intermediate step
+                if rng is not None and rng.device != dev:
+                    G[k].copy_(torch.randn((1, 1, Ln), generator=rng, device=rng.device, dtype=torch.float32))
+                else:
+                    torch.randn((1, 1, Ln), generator=rng, out=G[k])
+            try:
+                y = run(x, G)
+            except L.OuRangeError as e:
+                # as enhance(): widen the named layers' exponents (or fall back
+                # to f32 operands) and rerun the whole clip on the same noise
+                y = self._range_recover(e, lambda: run(x, G))
+            outs.append(y)
+        out = torch.stack(outs)
+        return out[0] if mix.ndim == 1 else out if mix.ndim == 2 else out[:, None, :]
 
     def enhance_many(self, mixes, n_steps: Optional[int] = None, epsilon: Optional[float] = None,
                      rng: Optional[torch.Generator] = None, keep_rms: Optional[bool] = False, streams: int = 2,
