@@ -231,9 +231,14 @@ typedef struct ou_gru_desc {
                                /* 128-unit workgroups, bit4 timing diagnostic     */
                                /* (skips the hand-off wait: wrong results), bit8  */
                                /* per-step gi prefetch instead of LDS-staged gi   */
-                               /* chunks (one item per chain); bits 12-14 XCD     */
-                               /* offset of the bit-0 chain layout, bit 15 keeps  */
-                               /* the defaults of bits 0-11                       */
+                               /* chunks (one item per chain), bit9 the earlier   */
+                               /* step loop of the k-split kernel instead of the  */
+                               /* straight-line one (one item per chain: packed   */
+                               /* dot products, peeled first / last step, no      */
+                               /* run-time branches; same bits in y and hstate;   */
+                               /* bits 1 and 8 imply bit9); bits 12-14 XCD offset */
+                               /* of the bit-0 chain layout, bit 15 keeps the     */
+                               /* defaults of bits 0-11                           */
     uint64_t* granules;        /* workspace: ou_gru_workspace_bytes()             */
     int32_t* status;           /* device int, set nonzero on spin timeout         */
     int32_t t_begin, t_end;    /* steps [t_begin, t_end) of the T-step sequences  */
@@ -254,6 +259,10 @@ typedef struct ou_gru_desc {
 } ou_gru_desc;
 
 int64_t ou_gru_workspace_bytes(int hidden, int batch);
+/* k-split kernel: the workgroups one launch keeps resident.  A batch whose
+ * chains (2 per item, hidden / 16 or hidden / 32 workgroups each) exceed it
+ * runs several items per chain, then several launches. */
+int ou_gru_ks_max_workgroups(void);
 int ou_gru(const ou_gru_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------

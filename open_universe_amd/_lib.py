@@ -189,6 +189,7 @@ EXPORTS = {
     "ou_conv_tile_ok": (c_int, [c_int, c_int]),
     "ou_conv_lds_info": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     "ou_gru_workspace_bytes": (c_int64, [c_int, c_int]),
+    "ou_gru_ks_max_workgroups": (c_int, []),
     "ou_gru": (c_int, [POINTER(GruDesc), c_void_p]),
     "ou_embed": (c_int, [POINTER(EmbedDesc), c_void_p]),
     "ou_head": (c_int, [POINTER(HeadDesc), c_void_p]),

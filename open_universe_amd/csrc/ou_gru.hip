@@ -25,6 +25,8 @@
 // dot products are reduced across the 8 kg lanes with xor-shuffles.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/ouhip.h"
 #include "ou_common.h"
 
@@ -275,6 +277,26 @@ __global__ __launch_bounds__(8 * U) void gru_kernel(ou_gru_desc d, int nb, int n
 // then an 8-lane DPP sum -- which leaves lane L with the r/z/n sums of unit
 // L >> 3 (replicated on 8 lanes).  Each lane keeps its unit's h_{t-1} in a
 // register; one lane per unit publishes h_t.
+//
+// The step.  h_t needs every workgroup's h_{t-1}, so a step is the hand-off
+// (granule store -> L2 -> the consumers' polls) plus everything a wave does
+// between the arrival of the last granule and its own granule store; that
+// serial part costs the whole chain 1:1.  Phase stamps (-DOU_GRU_STAMPS,
+// H = 256, one item per chain, clocks per step by issue time): the earlier
+// loop spent 826 of 1,730 there (dot products 370, gates + stores 440), the
+// straight-line loop spends 345 of 1,554 (44 + 110 + 191) -- the rest, about
+// 1,200 clocks, is the hand-off itself.  Two step loops share the prologue
+// and epilogue of the kernel:
+//  - the straight-line loop (LEGACY = false; the default for one item per
+//    chain): store kind and "has residual" chosen once before the loop, the
+//    first and the last step peeled, the dot products as v_pk_fma_f32 pairs of
+//    rows, and the granule stored as soon as h_t exists (the output follows
+//    it);
+//  - the earlier loop (LEGACY = true: flags bit9, or several items per chain,
+//    or the diagnostic bits 1 / 8), with its run-time branches and scalar dot
+//    products.
+// Both run the same IEEE operations in the same order per row: y and hstate
+// are bit-identical (tests/test_gpu_gru_step.py).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float fast_sigmoid(float x)
 {
@@ -300,10 +322,38 @@ __device__ __forceinline__ void swap16(float& x, float& y)
     y = __uint_as_float(r[1]);
 }
 
+// acc[i] += acc[i + N] for i < N; adjacent values add as v_pk_add_f32 pairs
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <int N>
+__device__ __forceinline__ void add_halves(float* acc)
+{
+    if constexpr (N % 2 == 0) {
+#pragma unroll
+        for (int i = 0; i < N; i += 2) {
+            const f32x2 s = (f32x2){acc[i], acc[i + 1]} + (f32x2){acc[i + N], acc[i + N + 1]};
+            acc[i] = s.x;
+            acc[i + 1] = s.y;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) acc[i] += acc[i + N];
+    }
+}
+
+// h_t = (1 - z) n + z h_{t-1} as two products and a sum, never a fused
+// multiply-add: what the NB == 1 step loop has always compiled to (its two
+// products pack into one v_pk_mul_f32), spelled out so that a second copy of
+// the loop cannot round differently
+__device__ __forceinline__ float blend_nofma(float z, float n, float hp)
+{
+#pragma clang fp contract(off)
+    return (1.0f - z) * n + z * hp;
+}
+
 constexpr int kKsWaves = 4;   // waves per workgroup
 
 
-template <int H, int NB, int UW>
+template <int H, int NB, int UW, bool LEGACY>
 __global__ __launch_bounds__(64 * kKsWaves) void gru_ks_kernel(ou_gru_desc d, int nb, int nchains, int flags,
                                                                int bofs)
 {
@@ -345,6 +395,16 @@ __global__ __launch_bounds__(64 * kKsWaves) void gru_ks_kernel(ou_gru_desc d, in
         for (int g = 0; g < 3; ++g)
 #pragma unroll
             for (int k = 0; k < KPL; ++k) w[u][g][k] = wbase[(int64_t)(g * H + ubase + u) * H + k];
+    // straight-line loop, NB == 1: the rows as register pairs (values 2p and
+    // 2p + 1 of the index u * 3 + g) for the packed dot products
+    f32x2 wp[NB == 1 && !LEGACY ? NV / 2 : 1][KPL];
+    if constexpr (NB == 1 && !LEGACY) {
+#pragma unroll
+        for (int p = 0; p < NV / 2; ++p)
+#pragma unroll
+            for (int k = 0; k < KPL; ++k)
+                wp[p][k] = (f32x2){w[(2 * p) / 3][(2 * p) % 3][k], w[(2 * p + 1) / 3][(2 * p + 1) % 3][k]};
+    }
     const float bhr = d.b_hh[dir * 3 * H + 0 * H + j];
     const float bhz = d.b_hh[dir * 3 * H + 1 * H + j];
     const float bhn = d.b_hh[dir * 3 * H + 2 * H + j];
@@ -418,14 +478,14 @@ __global__ __launch_bounds__(64 * kKsWaves) void gru_ks_kernel(ou_gru_desc d, in
     // so a step reads its four values with one ds_read_b128 issued before
     // the hand-off wait.  flags bit8 keeps the per-step prefetch (A/B runs).
     constexpr int CS = UW == 4 ? 128 : 64;   // steps per chunk (4 UW x CS x 4 B = 8 KB per wave)
-    const bool stage = NB == 1 && !(flags & 256);
+    const bool stage = NB == 1 && (!LEGACY || !(flags & 256));
     float4* gst = nullptr;
     if constexpr (NB == 1) {
         __shared__ float4 gst_all[kKsWaves][CS * UW];
         gst = gst_all[wave];
     }
     const int wv = __builtin_amdgcn_readfirstlane(wave);
-    auto stage_chunk = [&](int c0) {   // steps [c0, c0 + CS) (clamped to te - 1) -> LDS
+    auto stage_chunk = [&](int c0) __attribute__((always_inline)) {   // steps [c0, c0 + CS) (clamped to te - 1) -> LDS
         constexpr int NV4 = 4 * UW * CS / 64;   // values per lane
         const int ub = (member * kKsWaves + wv) * UW;
         float v[NV4];
@@ -466,6 +526,158 @@ __global__ __launch_bounds__(64 * kKsWaves) void gru_ks_kernel(ou_gru_desc d, in
     else prefetch(tb);
     OU_STAMP_INIT
 
+    if constexpr (!LEGACY) {
+        // Straight-line step loop: the default for one item per chain (flags
+        // bit9 keeps the loop below, which also serves NB > 1).  Everything a
+        // wave does between the arrival of the last granule and its own
+        // granule store costs the whole chain once per step.  So what never
+        // changes inside a launch is decided once, before the loop: the store
+        // kind (same-XCD or not) and "has residual" select one of four copies
+        // of it, and the first step (no poll) and step T - 1 (no granule) are
+        // peeled.  The steady body branches only on the poll's retry and,
+        // every CS steps, on the chunk boundary.  The arithmetic is the loop
+        // below's, operation for operation: y and hstate are bit-identical.
+        static_assert(NB == 1, "the straight-line loop carries one item per chain");
+        auto run = [&](auto local_c, auto res_c) __attribute__((always_inline)) -> bool {
+            constexpr bool LOCAL = decltype(local_c)::value, RES = decltype(res_c)::value;
+            const float res_scale = d.res_scale;
+            float* yrow = d.y + (int64_t)b0 * d.y_bstride + (int64_t)(dir * H + j) * d.y_cstride;
+            uint64_t* gpub = gran + (((int64_t)b0 * 2 + dir) * 2) * H + j;   // parity 0; parity 1 is H further
+            auto poll = [&](int t, float (&h)[KPL]) __attribute__((always_inline)) -> bool {   // h_{t-1}, this lane's k-slice
+                const uint32_t want = (uint32_t)t;
+                const int par = (t - 1) & 1;
+                for (uint32_t spins = 0;; ++spins) {
+                    bool ok = true;
+                    if constexpr (KPL % 2 == 0) {
+#pragma unroll
+                        for (int q = 0; q < KPL / 2; ++q) {
+                            // aux 16 = sc1: served by L2, never by this CU's L1
+                            const auto v = __builtin_amdgcn_raw_buffer_load_b128(grsrc, goff(b0, par) + 16 * q, 0, 16);
+                            h[2 * q] = __uint_as_float(v[0]);
+                            h[2 * q + 1] = __uint_as_float(v[2]);
+                            ok &= v[1] == want && v[3] == want;
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < KPL; ++k) {
+                            const uint64_t v = __hip_atomic_load(
+                                gran + ((((int64_t)b0 * 2 + dir) * 2 + par) * H + lane * KPL + k),
+                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            h[k] = __uint_as_float((uint32_t)v);
+                            ok &= (uint32_t)(v >> 32) == want;
+                        }
+                    }
+                    if (__all(ok)) return true;
+                    __builtin_amdgcn_s_sleep(1);
+                    if (spins > (1u << 23)) {        // ~seconds: the chain is dead
+                        if (lane == 0) atomicExch(d.status, 1);
+                        return false;
+                    }
+                    asm volatile("" ::: "memory");   // re-load every pass
+                }
+            };
+            // one step; sc = its slot in the LDS chunk.  FIRST: h is h0, no
+            // poll.  PUB: publish h_t (every step but T - 1).
+            auto step = [&](int t, int sc, auto first_c, auto pub_c) __attribute__((always_inline)) -> bool {
+                constexpr bool FIRST = decltype(first_c)::value, PUB = decltype(pub_c)::value;
+                float h[KPL];
+                // this step's staged gi / residual (LDS read in flight during the wait)
+                const float4 gv = gst[sc * UW + (lane >> USH)];
+                if constexpr (FIRST) {
+#pragma unroll
+                    for (int k = 0; k < KPL; ++k) h[k] = h0[0][k];
+                } else {
+                    if (!poll(t, h)) return false;
+                }
+                OU_STAMP(0);
+
+                // partial dot products, value index u * 3 + g: two rows per
+                // v_pk_fma_f32, h[k] broadcast to both halves; each row is
+                // still one fused multiply-add chain over k = 0..KPL-1
+                float acc[NV];
+#pragma unroll
+                for (int p = 0; p < NV / 2; ++p) {
+                    f32x2 a = {0.f, 0.f};
+#pragma unroll
+                    for (int k = 0; k < KPL; ++k) a = __builtin_elementwise_fma(wp[p][k], (f32x2){h[k], h[k]}, a);
+                    acc[2 * p] = a.x;
+                    acc[2 * p + 1] = a.y;
+                }
+                OU_STAMP(1);
+
+                // reduce-scatter as in the loop below; adjacent values add as pairs
+#pragma unroll
+                for (int i = 0; i < NV / 2; ++i) swap32(acc[i], acc[i + NV / 2]);
+                add_halves<NV / 2>(acc);
+#pragma unroll
+                for (int i = 0; i < NV / 4; ++i) swap16(acc[i], acc[i + NV / 4]);
+                add_halves<NV / 4>(acc);
+                if constexpr (UW == 8) {
+                    const bool hi8 = lane & 8;
+#pragma unroll
+                    for (int i = 0; i < NG; ++i) {
+                        const float send = hi8 ? acc[i] : acc[i + NG];
+                        const float keep = hi8 ? acc[i + NG] : acc[i];
+                        acc[i] = keep + OU_DPP(send, 0x128);   // row_ror:8 == lane ^ 8
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < NG; ++i) acc[i] += OU_DPP(acc[i], 0x128);
+                }
+#pragma unroll
+                for (int i = 0; i < NG; ++i) acc[i] = sum8(acc[i]);
+                OU_STAMP(2);
+
+                // only r -> n is serial: z's exp / rcp sit in the shadow of r's
+                const float r = fast_sigmoid(gv.x + (acc[0] + bhr));
+                const float z = fast_sigmoid(gv.y + (acc[1] + bhz));
+                const float n = fast_tanh(gv.z + r * (acc[2] + bhn));
+                const float hn = blend_nofma(z, n, hp[0]);
+                // the granule leaves as soon as hn exists; the output follows it
+                if constexpr (PUB) {
+                    if (writer) {
+                        const uint64_t gw = ((uint64_t)(uint32_t)(t + 1) << 32) | __float_as_uint(hn);
+                        uint64_t* gp = gpub + (t & 1) * H;
+                        if constexpr (LOCAL)   // plain 8-byte store: stays in the shared L2
+                            __hip_atomic_store(gp, gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        else                   // sc1 write-through
+                            __hip_atomic_store(gp, gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                hp[0] = hn;
+                if (writer) yrow[dir == 0 ? t : T - 1 - t] = RES ? (hn + gv.w) * res_scale : hn;
+                OU_STAMP(3);
+                return true;
+            };
+            constexpr std::true_type yes{};
+            constexpr std::false_type no{};
+            // steps [tb, tmid) publish; step T - 1 (when this launch has it) does not
+            const int tmid = min(te, T - 1);
+            if (tb < tmid) {
+                if (!step(tb, 0, yes, yes)) return false;
+            } else {
+                if (!step(tb, 0, yes, no)) return false;
+            }
+            // chunk boundary, right after a step's granule store (so it runs
+            // while the hand-off is in flight): the next gi chunk comes in
+            int sc = 1;
+            for (int t = tb + 1; t < tmid; ++t) {
+                if (!step(t, sc, no, yes)) return false;
+                if (++sc == CS && t + 1 < te) {
+                    stage_chunk(t + 1);
+                    sc = 0;
+                }
+            }
+            if (te == T && T - 1 > tb) {
+                if (!step(T - 1, sc, no, no)) return false;
+            }
+            return true;
+        };
+        bool done;
+        if (local_l2) done = d.res ? run(std::true_type{}, std::true_type{}) : run(std::true_type{}, std::false_type{});
+        else done = d.res ? run(std::false_type{}, std::true_type{}) : run(std::false_type{}, std::false_type{});
+        if (!done) return;
+    } else   // the earlier step loop, unchanged (its body keeps its indentation)
     for (int t = tb; t < te; ++t) {
         const int time = dir == 0 ? t : T - 1 - t;
         float h[NB][KPL];
@@ -625,8 +837,15 @@ void launch_ks(const ou_gru_desc& d, int nb, int nchains, int flags, int bofs, h
 {
     constexpr int G = H / (UW * kKsWaves);
     const int grid = (flags & 1) ? 8 * G * ((nchains + 7) / 8) : nchains * G;
-    hipLaunchKernelGGL((gru_ks_kernel<H, NB, UW>), dim3(grid), dim3(64 * kKsWaves), 0, s, d, nb, nchains, flags,
-                       bofs);
+    // bit9: the earlier step loop, which also carries several items per chain;
+    // its diagnostic variants (bit1 spin without s_sleep, bit8 per-step gi
+    // prefetch) exist only there
+    if (NB > 1 || (flags & (512 | 256 | 2)))
+        hipLaunchKernelGGL((gru_ks_kernel<H, NB, UW, true>), dim3(grid), dim3(64 * kKsWaves), 0, s, d, nb, nchains,
+                           flags, bofs);
+    else if constexpr (NB == 1)
+        hipLaunchKernelGGL((gru_ks_kernel<H, NB, UW, false>), dim3(grid), dim3(64 * kKsWaves), 0, s, d, nb, nchains,
+                           flags, bofs);
 }
 
 // items per launch of the k-split kernel: every workgroup of every chain must
@@ -696,6 +915,8 @@ extern "C" int64_t ou_gru_workspace_bytes(int hidden, int batch)
     return (xcc_slot_base(batch, hidden) + xcc_slot_count(batch, hidden) + (int64_t)kStampSlots * 1024) *
            (int64_t)sizeof(uint64_t);
 }
+
+extern "C" int ou_gru_ks_max_workgroups(void) { return kKsMaxWGs; }
 
 // after a launch: a short one (steps < 5) on a ws_zeroed workspace leaves it
 // zeroed for the next launch on it, whatever that one's T

@@ -1,5 +1,11 @@
 """Time the GRU recurrence variants (ou_gru_desc.flags) at score-network
-shape (H = 256, T = 801) for a few batch sizes; prints us per time step."""
+shape (H = 256, T = 801) for a few batch sizes; prints us per time step.
+
+GRU_FLAGS: the variants, the first one the reference of identical= (default:
+1 the straight-line step loop, 513 the earlier loop (bit9), then older
+variants); GRU_B: the batch sizes; GRU_REPS: passes over the flag list,
+alternating the variants in one process on one library (a summary line per
+variant follows: median and spread (max - min) of its passes' medians)."""
 import sys
 import os
 
@@ -23,12 +29,15 @@ def main():
     T = int(os.environ.get("GRU_T", "801"))
     stream = torch.cuda.current_stream().cuda_stream
     gw = eng.s_gru
-    for B in (1, 4, 8):
+    reps = int(os.environ.get("GRU_REPS", "1"))
+    for B in [int(b) for b in os.environ.get("GRU_B", "1,4,8").split(",")]:
         x = E.Act(torch.randn(B, 512, T, device=dev) * 0.5)
         gi, y = E.new_act(B, 1536, T, dev), E.new_act(B, 512, T, dev)
         gran = torch.zeros(L.load().ou_gru_workspace_bytes(256, B) // 8, dtype=torch.int64, device=dev)
         ref = None
-        for flags in [int(f) for f in os.environ.get("GRU_FLAGS", "5,7,9,11,21,25").split(",")]:
+        flag_list = [int(f) for f in os.environ.get("GRU_FLAGS", "1,513,5,7,9,11,21,25").split(",")]
+        meds = {f: [] for f in flag_list}
+        for flags in flag_list * reps:
             E.GRU_FLAGS = flags
             prog = L.Program()
             E.rec_gru(prog, gw, 0, x, gi, y, gran, eng.status)
@@ -43,8 +52,9 @@ def main():
                 ref = out
             ok = torch.equal(out, ref) and int(eng.status.max()) == 0
             eng.status.zero_()
-            print(f"B={B} flags={flags}: {1000 * min(ms) / T:.3f} us/step "
-                  f"(median {1000 * sorted(ms)[2] / T:.3f}) identical={ok}", flush=True)
+            meds[flags].append(1000 * sorted(ms)[2] / T)
+            print(f"B={B} flags={flags}: {1000 * min(ms) / T:.4f} us/step "
+                  f"(median {1000 * sorted(ms)[2] / T:.4f}) identical={ok}", flush=True)
             if os.environ.get("OUHIP_LIB", "").endswith("_diag.so"):
                 # phase stamps (OU_GRU_STAMPS build): cycles per step per workgroup
                 st = gran[B * 4 * 256 + B * 256 // 4:].view(-1, 8).cpu()
@@ -54,6 +64,10 @@ def main():
                 for w, r in enumerate(rows[:4]):
                     print("   wg%d " % w + " ".join(f"{n}={r[i] / r[5]:.0f}" for i, n in enumerate(names[:4])) + f" {names[4]}={r[4]}",
                           f"total={sum(r[:5]) / r[5]:.0f} cyc/step", flush=True)
+        if reps > 1:
+            for f, m in meds.items():
+                print(f"B={B} flags={f}: {reps} passes, median {sorted(m)[len(m) // 2]:.4f} us/step, "
+                      f"spread {max(m) - min(m):.4f}", flush=True)
 
 
 if __name__ == "__main__":
