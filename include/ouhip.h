@@ -229,7 +229,13 @@ typedef struct ou_gru_desc {
     int32_t flags;             /* -1 default; bit0 XCD-local chains, bit1 spin    */
                                /* without s_sleep, bit2 64-unit workgroups, bit3  */
                                /* 128-unit workgroups, bit4 timing diagnostic     */
-                               /* (skips the hand-off wait: wrong results), bit8  */
+                               /* (skips the hand-off wait: wrong results), bit5  */
+                               /* the workgroup-gather kernel instead of the      */
+                               /* k-split one (whole sequences only), bit6 no     */
+                               /* placement handshake (k-split kernel: every      */
+                               /* hand-off store is write-through; ou_gru sets it */
+                               /* itself for a launch of one step), bit7 8 units  */
+                               /* per wave instead of 4 (k-split kernel), bit8    */
                                /* per-step gi prefetch instead of LDS-staged gi   */
                                /* chunks (one item per chain), bit9 the earlier   */
                                /* step loop of the k-split kernel instead of the  */
@@ -246,7 +252,13 @@ typedef struct ou_gru_desc {
                                /* all.  A launch with t_begin > 0 starts from     */
                                /* hstate; every launch leaves h of its last step  */
                                /* there: the recurrence split over launches, each */
-                               /* ordered after the one before (k-split kernel)   */
+                               /* ordered after the one before (k-split kernel).  */
+                               /* A continuing range (t_begin > 0) holds at least */
+                               /* two steps: one step is refused (-2), because    */
+                               /* only a step's hand-off orders the workgroups'   */
+                               /* hstate stores after each other's loads.  One    */
+                               /* step from t_begin == 0 (T == 1 included) runs   */
+                               /* without the placement handshake (flags bit6)    */
     float* hstate;             /* [B][2][H], or NULL (whole sequences only)       */
     int32_t ws_zeroed;         /* nonzero: the caller zeroed the workspace before */
                                /* the first launch on it (per replay); launches   */

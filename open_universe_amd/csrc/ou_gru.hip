@@ -295,8 +295,9 @@ __global__ __launch_bounds__(8 * U) void gru_kernel(ou_gru_desc d, int nb, int n
 //  - the earlier loop (LEGACY = true: flags bit9, or several items per chain,
 //    or the diagnostic bits 1 / 8), with its run-time branches and scalar dot
 //    products.
-// Both run the same IEEE operations in the same order per row: y and hstate
-// are bit-identical (tests/test_gpu_gru_step.py).
+// Both run the same IEEE operations in the same order per row: y is
+// bit-identical (tests/test_gpu_gru_step.py), and so are hstate and the step
+// ranges [t_begin, t_end) of either loop (tests/test_gpu_gru_range.py).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float fast_sigmoid(float x)
 {
@@ -536,7 +537,8 @@ __global__ __launch_bounds__(64 * kKsWaves) void gru_ks_kernel(ou_gru_desc d, in
         // of it, and the first step (no poll) and step T - 1 (no granule) are
         // peeled.  The steady body branches only on the poll's retry and,
         // every CS steps, on the chunk boundary.  The arithmetic is the loop
-        // below's, operation for operation: y and hstate are bit-identical.
+        // below's, operation for operation: y and hstate are bit-identical
+        // (tests/test_gpu_gru_range.py).
         static_assert(NB == 1, "the straight-line loop carries one item per chain");
         auto run = [&](auto local_c, auto res_c) __attribute__((always_inline)) -> bool {
             constexpr bool LOCAL = decltype(local_c)::value, RES = decltype(res_c)::value;
@@ -818,7 +820,9 @@ __global__ __launch_bounds__(64 * kKsWaves) void gru_ks_kernel(ou_gru_desc d, in
     }
     // leave the placement slot zeroed for the next launch on this workspace:
     // every member of the chain has passed the placement handshake by now
-    // (none can finish step 1 before all have published step 0)
+    // (none can finish step 1 before all have published step 0; a launch of
+    // one step runs without the handshake, flags bit 6 set by ou_gru).  The
+    // same ordering keeps the hstate stores above behind every member's h0 loads
     if (!(flags & 64) && threadIdx.x == 0)
         __hip_atomic_store(gran + xcc_slot_base(d.batch, H) + ((int64_t)b0 * 2 + dir) * G + member, (uint64_t)0,
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -940,11 +944,23 @@ extern "C" int ou_gru(const ou_gru_desc* dp, void* stream)
     // set), bits 12-14 the XCD offset of the chain layout (bit 0)
     const bool dflt = d.flags < 0 || (d.flags & 0x8000);
     const int fbits = dflt ? -1 : (d.flags & 0xfff), fofs = d.flags >= 0 ? (d.flags & 0x7000) : 0;
-    if (d.t_begin < 0 || (d.t_end != 0 && (d.t_end <= d.t_begin || d.t_end > d.steps)) || (split && !d.hstate))
+    // t_end == 0 stands for steps: t_begin must leave at least one step
+    if (d.t_begin < 0 || d.t_begin >= d.steps || (d.t_end != 0 && (d.t_end <= d.t_begin || d.t_end > d.steps)) ||
+        (split && !d.hstate))
         return ou_fail(-1, "gru: bad step range [%d, %d) of %d (hstate %p)", d.t_begin, d.t_end, d.steps,
                        (const void*)d.hstate);
     if (split && (d.hidden % 64 || (fbits >= 0 && (fbits & 32))))
         return ou_fail(-2, "gru: a step range needs the k-split kernel (hidden %% 64 == 0)");
+    // A launch of one step has no poll, so nothing orders the workgroups of a
+    // chain after the placement handshake: a member could clear its slot
+    // before another has read it, or store its units of hstate before another
+    // has loaded h0 from it.  One step from t_begin == 0 reads no hstate and
+    // runs without the handshake (bit 6: a single step has no hand-off to
+    // speed up); a continuing range of one step is refused.
+    const bool one_step = (d.t_end != 0 ? d.t_end : d.steps) - d.t_begin == 1;
+    if (one_step && d.t_begin > 0)
+        return ou_fail(-2, "gru: a continuing step range holds at least two steps ([%d, %d) of %d)", d.t_begin,
+                       d.t_begin + 1, d.steps);
     if (!d.w_hh || !d.granules || !d.status) return ou_fail(-1, "gru: invalid descriptor");
     // the k-split kernel clears its placement slots when it exits.  A launch
     // of T steps leaves the tags T - 1 and T - 2 in the two parity slots (it
@@ -961,7 +977,7 @@ extern "C" int ou_gru(const ou_gru_desc* dp, void* stream)
     // k-split kernel (default for H % 64 == 0; flags bit5 selects the
     // workgroup-gather kernel below)
     if (d.hidden % 64 == 0 && !(fbits >= 0 && (fbits & 32))) {
-        const int kflags = (fbits >= 0 ? fbits : 1) | fofs;
+        const int kflags = (fbits >= 0 ? fbits : 1) | fofs | (one_step ? 64 : 0);
         switch (d.hidden) {
         case 64: launch_ks_all<64>(d, kflags, s); break;
         case 128: launch_ks_all<128>(d, kflags, s); break;
