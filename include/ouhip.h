@@ -53,6 +53,43 @@ const char* ou_last_error(void);
  *   v = (v + res1[b][co][t]) * s1;  v = film_g[b][co]*v + film_b[b][co];
  *   v = (v + res2[b][co][t]) * s2;  y[b][co][t] = v   for t < out_len
  * ---------------------------------------------------------------------- */
+
+/* ou_conv_desc.tile: -1 = ou_conv's static choice (ou_conv_pick_tile), else
+ * one word that selects the kernel family, its shape and its variants.  The
+ * first of OU_TILE_FIR / _SS / _RS that is set names the family; without
+ * them OU_TILE_WS, then a tiles-per-workgroup field > 0, then neither.
+ *
+ *   family             shape id (bits 0-7)  bits 8-9          other legal fields
+ *   plain (one tile)   < ou_conv_num_tiles  0                 K slices, m-major
+ *   persistent         same, no split-K     log2(tiles / WG)  -
+ *   warp-specialised   same, ids 0-12       0                 -
+ *   register-streamed  0-5                  diagnostic mode   K slices, m-major
+ *   split-image        0-5 (NR - 1, + 3)    0                 m-major
+ *   FIR                0-7                  early / deep      m-major
+ *
+ * Persistent and warp-specialised are f32 (prec 0) kernels and need f0 = 0;
+ * register-streamed, split-image and FIR need prec 1 / 2 (split-image: 1).
+ * K slices S > 1 need the workspace ks_ws.  ou_conv_tile_ok() says whether a
+ * word is well formed and fits LDS at a tap count; ou_conv() itself also
+ * takes the diagnostic modes, which ou_conv_tile_ok() refuses. */
+#define OU_TILE_SHAPE_MASK 0xff
+#define OU_TILE_TPW_SHIFT 8             /* plain: log2(output tiles per workgroup) */
+#define OU_TILE_TPW_MASK (3 << 8)
+#define OU_TILE_WS (1 << 10)            /* warp-specialised persistent kernel */
+#define OU_TILE_SPLIT_QUERY (1 << 11)   /* ou_conv_tile_ok / ou_conv_lds_info only: */
+                                        /* the plain shape's prec 1 / 2 form        */
+#define OU_TILE_KS_SHIFT 12             /* log2(K slices S) */
+#define OU_TILE_KS_MASK (3 << 12)
+#define OU_TILE_RS (1 << 14)            /* register-streamed kernel */
+#define OU_TILE_SS (1 << 15)            /* split-image input kernel (desc.xs) */
+#define OU_TILE_MMAJOR (1 << 16)        /* m-groups fastest in the workgroup order */
+#define OU_TILE_FIR (1 << 17)           /* FIR-applied rate-change kernels (desc.fir) */
+#define OU_TILE_FIR_EARLY (1 << 8)      /* FIR, up (fir 2): epilogue loads before the main loop */
+#define OU_TILE_FIR_DEEP (1 << 9)       /* FIR, lean down (fir 1) or up without EARLY: */
+                                        /* two input chunks in flight per thread       */
+#define OU_TILE_RS_DIAG_SHIFT 8         /* register-streamed: 1 no input loads, 2 no K loop */
+#define OU_TILE_RS_DIAG_MASK (3 << 8)
+
 typedef struct ou_conv_desc {
     const float* x;            /* input signal                                   */
     int64_t x_bstride;         /* elements between batch items                   */
@@ -86,10 +123,7 @@ typedef struct ou_conv_desc {
     const float* res2;         /* residual 2 or NULL                             */
     int64_t r2_bstride, r2_cstride;
     float s2;
-    int32_t tile;              /* -1 = auto; bits 0-7 tile shape (< ou_conv_     */
-                               /* num_tiles()), bits 8-9 log2(output tiles per   */
-                               /* workgroup; > 0: persistent kernel, see         */
-                               /* ou_conv_tile_ok)                               */
+    int32_t tile;              /* -1 = auto, else an OU_TILE_* word (above)      */
     int32_t prec;              /* 0: f32 operands (weights from ou_conv_pack);   */
                                /* 1: split-f16 operands (ou_conv_pack_split),    */
                                /*    f32-class accuracy, see ou_conv.hip;        */
@@ -101,11 +135,11 @@ typedef struct ou_conv_desc {
                                /* frame coordinates of x / y (zero padding only  */
                                /* at the true ends); 0 = from the start.  The    */
                                /* persistent / warp-specialised f32 kernels      */
-                               /* (tile bits 8-10) need f0 = 0                   */
+                               /* need f0 = 0                                    */
     int32_t* status;           /* prec 1 / 2: range codes (xs_shift) are OR-ed   */
                                /* in here, or NULL                               */
-    float* ks_ws;              /* K-slice workspace (tile bits 12-13 = log2 S,   */
-    int64_t ks_ws_bytes;       /* S > 1): S partial sums per output tile, then   */
+    float* ks_ws;              /* K-slice workspace (OU_TILE_KS_*: S > 1 slices) */
+    int64_t ks_ws_bytes;       /* S partial sums per output tile, then           */
                                /* a reduce + epilogue launch; NULL if unused     */
     /* Split images (prec 1).  The operand of the NEXT conv, stored once by
      * its producer's epilogue so that the consumer stages it with plain
@@ -122,7 +156,7 @@ typedef struct ou_conv_desc {
     int32_t sy_shift;          /* the consumer's staging exponent                */
     float sy_slope;            /* the consumer's PReLU slope                     */
     int32_t sy_pad_;
-    const uint16_t* xs;        /* consumer (tile bit 15, conv_skernel): read the */
+    const uint16_t* xs;        /* consumer (OU_TILE_SS, conv_skernel): read the  */
                                /* PReLU'd operand from this split image instead  */
                                /* of x (x, slope and in_scale unused; weights    */
                                /* from ou_conv_pack_split_nat; cin % 32 == 0)    */
@@ -138,7 +172,7 @@ typedef struct ou_conv_desc {
                                /* (with 1 / 2, ou_block's codes too): a finite   */
                                /* staged value reached 2^23 / 2^31 / 2^39        */
     /* Anti-aliased rate-change convs with the binomial FIR applied instead of
-     * folded into the weights (tile bit 17; PReLU_Conv with use_antialiasing,
+     * folded into the weights (OU_TILE_FIR; PReLU_Conv with use_antialiasing,
      * blocks.py:214-226, BinomialAntiAlias blocks.py:123-134):
      *   fir 1: f = FIR(prelu(x)) ('same', zero outside [0, in_len)), then the
      *          strided conv over f's frame view: frame = R, rout 1, K = cin R;
@@ -185,8 +219,8 @@ int ou_conv_pack(const float* w_logical, int m, int cin_eff, int kt, int cc,
  * kernel stages the input as x * 2^-6). */
 int ou_conv_pack_split(const float* w_logical, int m, int cin_eff, int kt,
                        float* packed, float* w_unscale);
-/* The same, in the natural channel order of the split-image kernel (tile bit
- * 15): [m-tile][16-channel group g][hi | lo][tap][lane][8 halves], lane l
+/* The same, in the natural channel order of the split-image kernel
+ * (OU_TILE_SS): [m-tile][16-channel group g][hi | lo][tap][lane][8 halves], lane l
  * holding row l & 31 and channel 16*g + 8*(l >> 5) + j in half j -- a lane's
  * B operand is then 8 consecutive channels of one split-image row. */
 int ou_conv_pack_split_nat(const float* w_logical, int m, int cin_eff, int kt,

@@ -359,7 +359,7 @@ def conv_pack_split_np(w_logical):
 def conv_pack_split_nat_np(w_logical):
     """ou_conv_pack_split_nat restated with numpy (byte-identical): [mt][g]
     [hi|lo][k][lane = h*32 + r][j] of a[mt*32 + r][16 g + 8 h + j][k] -- the
-    natural channel order of the split-image kernel (tile bit 15)."""
+    natural channel order of the split-image kernel (TILE_SS)."""
     import numpy as np
 
     w = np.ascontiguousarray(w_logical, dtype=np.float32)
@@ -447,21 +447,32 @@ def block_pack(w_logical):
     return out, float(un.value)
 
 
-# tile bit 16 (ou_conv.hip kMajBit): m-groups fastest in the workgroup order,
-# so every input window is fetched from HBM once and re-read by its other
-# m-groups from the XCD's L2.  Chosen for inputs too large to stay in the
+# ConvDesc.tile fields: the OU_TILE_* constants of include/ouhip.h, which gives
+# the layout per kernel family (tests/test_abi.py compares the two)
+TILE_SHAPE_MASK = 0xff
+TILE_TPW_SHIFT, TILE_TPW_MASK = 8, 3 << 8      # plain shapes: log2(output tiles per workgroup)
+TILE_WS = 1 << 10                              # warp-specialised persistent kernel
+TILE_SPLIT_QUERY = 1 << 11                     # ou_conv_tile_ok / ou_conv_lds_info: the prec 1 / 2 form
+TILE_KS_SHIFT, TILE_KS_MASK = 12, 3 << 12      # log2(K slices)
+TILE_RS = 1 << 14                              # register-streamed kernel (conv_rkernel)
+TILE_SS = 1 << 15                              # split-image kernel (conv_skernel), shape = NR - 1
+TILE_MMAJOR = 1 << 16                          # m-groups fastest in the workgroup order
+TILE_FIR = 1 << 17                             # FIR-applied rate-change kernels
+TILE_FIR_EARLY = 1 << 8    # with TILE_FIR: the up kernel's residual / bias loads issued before its main loop
+TILE_FIR_DEEP = 1 << 9     # with TILE_FIR: two input chunks in flight per thread (lean down, up)
+TILE_RS_DIAG_SHIFT, TILE_RS_DIAG_MASK = 8, 3 << 8   # with TILE_RS: diagnostic mode (tools/conv_bench.py --rdiag)
+MAJ_BIT, SS_BIT, FIR_BIT = TILE_MMAJOR, TILE_SS, TILE_FIR   # earlier names, kept for callers outside the package
+
+# TILE_MMAJOR: every input window is fetched from HBM once and re-read by its
+# other m-groups from the XCD's L2.  Chosen for inputs too large to stay in the
 # caches between m-groups (OUHIP_MMAJOR_MB, default 128 MB of input per
 # launch; OUHIP_MMAJOR=0 never): the batched long-signal levels (C4).
-MAJ_BIT = 1 << 16
 _MMAJOR = os.environ.get("OUHIP_MMAJOR", "1") != "0"
 _MMAJOR_BYTES = float(os.environ.get("OUHIP_MMAJOR_MB", "128")) * 2**20
 
 
-FIR_BIT = 1 << 17   # FIR-applied rate-change kernels (bits 0-7 shape, bit 8 early epilogue loads)
-
-
 def mmajor_order(desc):
-    multi = desc.tile & ((3 << 8) | (1 << 10)) and not desc.tile & FIR_BIT
+    multi = desc.tile & (TILE_TPW_MASK | TILE_WS) and not desc.tile & TILE_FIR
     if not _MMAJOR or multi:   # one-tile, register-streamed and FIR kernels only
         return False
     in_bytes = 4.0 * desc.batch * desc.cin * desc.frame * desc.n_frames
@@ -475,7 +486,6 @@ TUNER = None
 
 ADD_HOOK = None   # engine.split_hook while a plan records: links an op to its producer's split image
                  # (ADD_HOOK.note(prog, index, op, desc) then sees every op added)
-SS_BIT = 1 << 15  # ConvDesc.tile bit: the split-image kernel (conv_skernel), bits 0-7 = NR - 1
 
 
 class Program:
@@ -504,7 +514,7 @@ class Program:
         if op == OP_CONV and desc.tile < 0 and TUNER is not None:
             desc.tile = TUNER(desc)
         if op == OP_CONV and desc.tile >= 0 and mmajor_order(desc):
-            desc.tile |= MAJ_BIT
+            desc.tile |= TILE_MMAJOR
         check(self.lib.ou_program_add(self.h, op, ctypes.byref(desc), ctypes.sizeof(desc)),
               f"program_add(op={op})")
         if ADD_HOOK is not None and hasattr(ADD_HOOK, "note"):

@@ -41,6 +41,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/ouhip.h"
 #include "ou_common.h"
@@ -82,9 +83,13 @@ struct Cfg {
 };
 
 constexpr int kSentinel = 0x7ffffff0;   // byte offset past any buffer: loads return 0
-// tile bit 16: m-groups fastest in the workgroup order (ou_xcd_block_m), for
-// inputs much larger than the weights; the one-tile and register-streamed kernels
-constexpr int kMajBit = 1 << 16;
+// ou_conv_desc.tile fields (include/ouhip.h gives the layout per kernel family).
+// kMajBit: m-groups fastest in the workgroup order (ou_xcd_block_m), for
+// inputs much larger than the weights
+constexpr int kMajBit = OU_TILE_MMAJOR;
+[[maybe_unused]] constexpr int kWsBit = OU_TILE_WS, kSplitBit = OU_TILE_SPLIT_QUERY, kRsBit = OU_TILE_RS,
+                               kSsBit = OU_TILE_SS, kFirBit = OU_TILE_FIR, kFirEarly = OU_TILE_FIR_EARLY,
+                               kFirDeep = OU_TILE_FIR_DEEP;
 
 // Diagnostic build only (-DOU_CONV_STAMPS, tools/conv_bench.py --stamps):
 // thread 0 of each of the first kStampWGs workgroups sums s_memtime deltas
@@ -2430,13 +2435,11 @@ __global__ __launch_bounds__(256 + 64 * kWsLoaders) void conv_wkernel(ou_conv_de
 // workgroup reads each input sample once (the frame-view kernels' phase-major
 // chunks re-read every line once per chunk of phases).
 // ---------------------------------------------------------------------------
-[[maybe_unused]] constexpr int kFirBit = 1 << 17;
-// tile bit 9 (down fir 1 without residuals / FiLM, up without bit 8): two
+// kFirDeep (down fir 1 without residuals / FiLM, up without kFirEarly): two
 // input chunks in flight per thread (PD = 2) -- the raw x window of chunk
 // q + 2 is requested while chunk q's MFMAs run, for the layers whose chunks
-// are too short to cover an HBM round trip; costs 10-60 VGPRs
-[[maybe_unused]] constexpr int kFirDeep = 1 << 9;
-[[maybe_unused]] constexpr int kFirEarly = 1 << 8;   // up (fir 2): epilogue loads before the main loop
+// are too short to cover an HBM round trip; costs 10-60 VGPRs.
+// kFirEarly (up, fir 2): epilogue loads before the main loop
 
 template <int R, int WM, int WN, int MR, int NR>
 struct FCfg {
@@ -3065,8 +3068,130 @@ constexpr Tile kTiles[] = {OU_TILES(OU_TILE_ENTRY)};
 #undef OU_TILE_ENTRY
 [[maybe_unused]] constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
 
+// register-streamed shapes: id, WM (32-row m-tiles), WK (K parts), NR (32-frame tiles)
+#define OU_RTILES(X) X(0, 2, 2, 1) X(1, 2, 2, 2) X(2, 4, 1, 1) X(3, 1, 4, 1) X(4, 4, 1, 2) X(5, 1, 4, 2)
+[[maybe_unused]] constexpr int kNumRTiles = 6;
+
+// split-image shapes: id = NR - 1 (32 NR frames per workgroup), + 3: rows
+// prefetched U - 0.5 chunks ahead instead of half a chunk (more VGPRs: one
+// wave per SIMD at NR 2 / 3)
+[[maybe_unused]] constexpr int kNumSTiles = 6;
+
+// FIR shapes: id, WM, WN, MR, NR (BM = 32 WM MR rows, BN = 32 WN NR frames)
+#define OU_FTILES(X) \
+    X(0, 2, 2, 1, 1) X(1, 4, 1, 1, 2) X(2, 2, 2, 2, 1) X(3, 1, 4, 2, 1) X(4, 2, 2, 1, 2) X(5, 4, 1, 2, 1) \
+    X(6, 2, 2, 2, 2) X(7, 4, 1, 1, 1)
+[[maybe_unused]] constexpr int kNumFTiles = 8;
+
+}  // namespace
+
+// ---- the tile word, decoded (host only) --------------------------------------
+// ou_conv_desc.tile taken apart once; include/ouhip.h has the layout.  At
+// global scope because the per-tap and per-rate units' entry points take it.
+enum ou_tile_family { kPlain, kPersistent, kWarpSpec, kRegStream, kSplitImage, kFir };
+struct ou_tile_word {
+    ou_tile_family family;
+    int shape;          // index into the family's shape table
+    int tpw;            // output tiles per workgroup (> 1: kPersistent)
+    int kslices;        // K slices S
+    bool mmajor;
+    bool fir_early, fir_deep;
+    int diag;           // register-streamed diagnostic mode
+    bool split;         // query bit: the plain shape's prec 1 / 2 form
+    const char* fault;  // why the word is malformed for its family, or nullptr
+};
+
+namespace {
+
+// The two readers of a tile word differ, and always have:
+//  kLaunch  ou_conv().  Words of the three plain families (no FIR / split-
+//           image / register-streamed bit) are read leniently: a shape id past
+//           the table is replaced by the static choice, bits 11 and 18 up and
+//           the tiles-per-workgroup field under kWsBit are ignored, and a
+//           split-K or 'big' shape the persistent / warp-specialised kernel
+//           lacks fails in the launcher, after the descriptor checks.  The
+//           register-streamed diagnostic modes are legal.  The tap count is
+//           checked where the kernel is chosen, not here.
+//  kQuery   ou_conv_tile_ok(), vouching for words the tuner will time: all of
+//           the above is refused and the tap count checked, but the K-slice
+//           field and bits 18 up of a plain / persistent word are not looked at.
+enum TileUse { kLaunch, kQuery };
+
+[[maybe_unused]] ou_tile_word decode_tile(int tile, int kt, TileUse use)
+{
+    ou_tile_word w{};
+    const int f89 = (tile & OU_TILE_TPW_MASK) >> OU_TILE_TPW_SHIFT;   // bits 8-9: meaning by family
+    w.shape = tile & OU_TILE_SHAPE_MASK;
+    w.tpw = 1;
+    w.kslices = 1 << ((tile & OU_TILE_KS_MASK) >> OU_TILE_KS_SHIFT);
+    w.mmajor = tile & kMajBit;
+    w.split = tile & kSplitBit;
+    const bool kt135 = kt == 1 || kt == 3 || kt == 5;
+    int legal = OU_TILE_SHAPE_MASK, nshapes = kNumTiles;
+    bool kt_ok = true;
+    if (tile & kFirBit) {
+        w.family = kFir;
+        w.fir_early = tile & kFirEarly, w.fir_deep = tile & kFirDeep;
+        legal |= kFirBit | kMajBit | kFirEarly | kFirDeep, nshapes = kNumFTiles, kt_ok = kt == 1;
+    } else if (tile & kSsBit) {
+        w.family = kSplitImage;
+        legal |= kSsBit | kMajBit, nshapes = kNumSTiles, kt_ok = kt135;
+    } else if (tile & kRsBit) {
+        w.family = kRegStream;
+        w.diag = f89;
+        legal |= kRsBit | kMajBit | OU_TILE_KS_MASK | (use == kLaunch ? OU_TILE_RS_DIAG_MASK : 0);
+        nshapes = kNumRTiles, kt_ok = kt135;
+    } else {
+        const bool ws = tile & kWsBit;
+        w.tpw = ws ? 1 : 1 << f89;
+        w.family = ws ? kWarpSpec : w.tpw > 1 ? kPersistent : kPlain;
+        if (use == kLaunch) {
+            if (w.kslices > 1 && w.family != kPlain) w.fault = "K slices need the one-tile kernel";
+            else if (w.mmajor && w.family != kPlain) w.fault = "the m-major order needs the one-tile kernel";
+            return w;
+        }
+        if (w.split) legal |= kSplitBit | kMajBit;   // one-tile workgroups, no other bits
+        else if (ws) legal |= kWsBit;
+        else legal = w.family == kPlain ? ~0 : ~kMajBit;
+    }
+    if ((tile & ~legal) || w.shape >= nshapes) w.fault = "a bit or shape id its kernel family does not have";
+    else if (use == kQuery && !kt_ok) w.fault = "no kernel of its family for the tap count";
+    else if (use == kQuery && w.family == kWarpSpec && kTiles[w.shape].big) w.fault = "no warp-specialised form";
+    else if (use == kQuery && w.family == kPersistent && kTiles[w.shape].wk != 1)
+        w.fault = "tiles per workgroup > 1 need a shape without split-K";
+    return w;
+}
+
 constexpr int kMaxLds = 160 * 1024;     // gfx950: 160 KiB per CU
 constexpr int kLdsTwoPerCu = 80 * 1024; // fits two workgroups per CU
+
+// packed weights (ou_conv_pack*): 32-row m-tiles, the channel axis padded to kCinAlign
+struct PackedGeom {
+    int mtiles, cin_eff, cin_pad;
+    int64_t a_mt_stride;   // floats per m-tile
+};
+PackedGeom packed_geom(int m, int cin, int frame, int kt)
+{
+    PackedGeom g;
+    g.mtiles = (m + 31) / 32;
+    g.cin_eff = cin * frame;
+    g.cin_pad = (g.cin_eff + kCinAlign - 1) / kCinAlign * kCinAlign;
+    g.a_mt_stride = (int64_t)g.cin_pad * kt * 32;
+    return g;
+}
+
+// opt in to more than 64 KiB of dynamic LDS, once per kernel
+template <auto Kern>
+int lds_opt_in(int bytes)
+{
+    static bool done = false;
+    if (!done && bytes > 64 * 1024) {
+        OU_HIP_CHECK(hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes),
+                     "conv: LDS attribute");
+        done = true;
+    }
+    return 0;
+}
 
 // channel chunk: the largest of 64/32/16/8 that splits over the K waves and
 // whose double-buffered stage fits two workgroups per CU, else one per CU
@@ -3122,22 +3247,17 @@ constexpr int lds_bytes_t()
 }
 
 template <int KT, int WM, int WN, int WK, int MR, int NR, int BIG, int P = 0>
-int launch_t(const ou_conv_desc& d, int tpw, hipStream_t s)
+int launch_t(const ou_conv_desc& d, int S, hipStream_t s)   // one output tile per workgroup, S K slices
 {
     constexpr int CC = P ? chunk_for_split<KT, WM, WN, WK, MR, NR, BIG>() : chunk_for<KT, WM, WN, WK, MR, NR, BIG>();
     if constexpr (CC == 0) {
-        (void)tpw;
+        (void)S;
         (void)s;
         return ou_fail(-2, "conv: tile shape has no split-f16 form (m %d, kt %d)", d.m, d.kt);
     } else {
     using C = Cfg<KT, CC, WM, WN, WK, MR, NR, P>;
-    const int mtiles = (d.m + 31) / 32;
-    const int cin_eff = d.cin * d.frame;
-    const int cin_pad = (cin_eff + kCinAlign - 1) / kCinAlign * kCinAlign;
+    const auto [mtiles, cin_eff, cin_pad, a_mt_stride] = packed_geom(d.m, d.cin, d.frame, KT);
     const int nchunks = (cin_eff + CC - 1) / CC;
-    const int64_t a_mt_stride = (int64_t)cin_pad * KT * 32;
-    (void)tpw;   // one output tile per workgroup
-    const int S = d.tile >= 0 ? 1 << ((d.tile >> 12) & 3) : 1;   // K slices
     dim3 grid((d.n_frames + C::BN - 1) / C::BN, (mtiles + WM * MR - 1) / (WM * MR), d.batch);
     if (S > 1) {
         const int64_t need = (int64_t)grid.x * grid.y * grid.z * S * C::BM * C::BN * 4;
@@ -3148,14 +3268,8 @@ int launch_t(const ou_conv_desc& d, int tpw, hipStream_t s)
     }
     const int slice_chunks = S > 1 ? (nchunks + S - 1) / S : nchunks;
     const int lds = (slice_chunks > 1 ? C::LDS2 : C::LDS1) * (int)sizeof(float);
-    auto kern = conv_kernel<KT, CC, WM, WN, WK, MR, NR, P>;
-    static bool attr = false;   // opt in to more than 64 KiB of dynamic LDS, once
-    if (!attr && C::LDS2 * 4 > 64 * 1024) {
-        OU_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         C::LDS2 * 4),
-                     "conv: LDS attribute");
-        attr = true;
-    }
+    constexpr auto kern = conv_kernel<KT, CC, WM, WN, WK, MR, NR, P>;
+    if (int rc = lds_opt_in<kern>(C::LDS2 * 4)) return rc;
     if (S == 1) {
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, d, nchunks, mtiles, a_mt_stride, 0);
         return ou_check_launch("conv");
@@ -3177,22 +3291,14 @@ int launch_p(const ou_conv_desc& d, int tpw, hipStream_t s)
     } else {
         constexpr int CC = chunk_for<KT, WM, WN, WK, MR, NR, BIG>();
         using C = Cfg<KT, CC, WM, WN, WK, MR, NR>;
-        const int mtiles = (d.m + 31) / 32;
-        const int cin_eff = d.cin * d.frame;
-        const int cin_pad = (cin_eff + kCinAlign - 1) / kCinAlign * kCinAlign;
+        const auto [mtiles, cin_eff, cin_pad, a_mt_stride] = packed_geom(d.m, d.cin, d.frame, KT);
         const int nchunks = (cin_eff + CC - 1) / CC;
-        const int64_t a_mt_stride = (int64_t)cin_pad * KT * 32;
         const int ntn = (d.n_frames + C::BN - 1) / C::BN;
         const int mgroups = (mtiles + WM * MR - 1) / (WM * MR);
         const int ntiles = ntn * mgroups * d.batch;
         const int lds = 2 * C::STAGE * (int)sizeof(float);
-        auto kern = conv_pkernel<KT, CC, WM, WN, MR, NR>;
-        static bool attr = false;
-        if (!attr && lds > 64 * 1024) {
-            OU_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds),
-                         "conv: LDS attribute");
-            attr = true;
-        }
+        constexpr auto kern = conv_pkernel<KT, CC, WM, WN, MR, NR>;
+        if (int rc = lds_opt_in<kern>(lds)) return rc;
         hipLaunchKernelGGL(kern, dim3((ntiles + tpw - 1) / tpw), dim3(256), lds, s, d, nchunks, mtiles, a_mt_stride,
                            ntn, mgroups, ntiles);
         return ou_check_launch("conv");
@@ -3229,27 +3335,20 @@ int launch_w(const ou_conv_desc& d, hipStream_t s)
     constexpr int CC = wchunk_for<KT, WM, WN, WK, MR, NR>();
     using C = WCfg<KT, CC, WM, WN, WK, MR, NR, kWStages>;
     constexpr int lds = C::LDS * 4;
-    const int mtiles = (d.m + 31) / 32;
-    const int cin_eff = d.cin * d.frame;
-    const int cin_pad = (cin_eff + kCinAlign - 1) / kCinAlign * kCinAlign;
+    const auto [mtiles, cin_eff, cin_pad, a_mt_stride] = packed_geom(d.m, d.cin, d.frame, KT);
     const int nchunks = (cin_eff + CC - 1) / CC;
     if (nchunks < 2)   // one accumulator image: two tiles' last chunks must be a tick apart
         return ou_fail(-2, "conv: warp-specialised tile needs >= 2 K chunks (cin_eff %d, chunk %d)", cin_eff, CC);
-    const int64_t a_mt_stride = (int64_t)cin_pad * KT * 32;
     const int ntn = (d.n_frames + C::BN - 1) / C::BN;
     const int mgroups = (mtiles + WM * MR - 1) / (WM * MR);
     const int ntiles = ntn * mgroups * d.batch;
-    auto kern = conv_wkernel<KT, CC, WM, WN, WK, MR, NR, kWStages>;
-    static bool attr = false;
-    static int per_cu = 1;
-    if (!attr) {
-        if (lds > 64 * 1024)
-            OU_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds),
-                         "conv: LDS attribute");
+    constexpr auto kern = conv_wkernel<KT, CC, WM, WN, WK, MR, NR, kWStages>;
+    if (int rc = lds_opt_in<kern>(lds)) return rc;
+    static int per_cu = 0;   // workgroups per CU, queried once
+    if (per_cu == 0) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256 + 64 * kWsLoaders, lds) == hipSuccess && n > 0)
-            per_cu = n;
-        attr = true;
+        per_cu = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256 + 64 * kWsLoaders, lds) == hipSuccess && n > 0
+                     ? n : 1;
     }
     if (g_num_cus <= 0) {
         int dev = 0;
@@ -3263,42 +3362,22 @@ int launch_w(const ou_conv_desc& d, hipStream_t s)
     return ou_check_launch("conv");
 }
 
-constexpr int kWsBit = 1 << 10;   // tile bit: warp-specialised persistent kernel
-constexpr int kRsBit = 1 << 14;   // tile bit: register-streamed kernel (conv_rkernel)
-constexpr int kSplitBit = 1 << 11;   // tile-query bit (LDS size, tile_ok): the split-f16 kernel
-
+// LDS bytes of a plain-table shape: its split-f16 form (query bit), its
+// warp-specialised form, else the f32 one-tile / persistent form; -1 = none
 template <int KT>
-int lds_bytes_kt(int tile)
+int lds_bytes_kt(const ou_tile_word& w)
 {
-    if (tile & kSplitBit) {
-        switch (tile & 0xff) {
-#define OU_TILE_CASE(id, wm, wn, wk, mr, nr, big) case id: return lds_bytes_split_t<KT, wm, wn, wk, mr, nr, big>();
-            OU_TILES(OU_TILE_CASE)
-#undef OU_TILE_CASE
-        }
-        return -1;
-    }
-    if (tile & kWsBit) {
-        switch (tile & 0xff) {
-#define OU_TILE_CASE(id, wm, wn, wk, mr, nr, big) \
-    case id: return big ? -1 : wlds_bytes_t<KT, wm, wn, wk, mr, nr>();
-            OU_TILES(OU_TILE_CASE)
-#undef OU_TILE_CASE
-        }
-        return -1;
-    }
-    switch (tile & 0xff) {
-#define OU_TILE_CASE(id, wm, wn, wk, mr, nr, big) case id: return lds_bytes_t<KT, wm, wn, wk, mr, nr, big>();
+    switch (w.shape) {
+#define OU_TILE_CASE(id, wm, wn, wk, mr, nr, big)                                                          \
+    case id:                                                                                               \
+        return w.split                 ? lds_bytes_split_t<KT, wm, wn, wk, mr, nr, big>()                   \
+               : w.family == kWarpSpec ? (big ? -1 : wlds_bytes_t<KT, wm, wn, wk, mr, nr>())                \
+                                       : lds_bytes_t<KT, wm, wn, wk, mr, nr, big>();
         OU_TILES(OU_TILE_CASE)
 #undef OU_TILE_CASE
     }
     return -1;
 }
-
-
-// register-streamed shapes (tile bit 14): id, WM (32-row m-tiles), WK (K parts), NR (32-frame tiles)
-#define OU_RTILES(X) X(0, 2, 2, 1) X(1, 2, 2, 2) X(2, 4, 1, 1) X(3, 1, 4, 1) X(4, 4, 1, 2) X(5, 1, 4, 2)
-[[maybe_unused]] constexpr int kNumRTiles = 6;
 
 // K chunking of the register-streamed kernel: the whole window (pc = R
 // phases x cch = cin channels) when it fits LDS, else chunks of at most half
@@ -3326,28 +3405,19 @@ bool rchunks(int cin, int rf, int* pc, int* cch)
 }
 
 template <int KT, int WM, int WK, int NR, int P>
-int launch_r(const ou_conv_desc& d, hipStream_t s)
+int launch_r(const ou_conv_desc& d, int S, hipStream_t s)   // S K slices
 {
     using R = RCfg<KT, WM, WK, NR>;
     int pc = 0, cch = 0;
     if (!rchunks<KT, WM, WK, NR, P>(d.cin, d.frame, &pc, &cch))
         return ou_fail(-2, "conv: no register-streamed K chunking for cin %d x frame %d", d.cin, d.frame);
-    const int S = 1 << ((d.tile >> 12) & 3);   // K slices
     const int nchunks = (d.frame / pc) * (d.cin / cch);
     if (S > nchunks)
         return ou_fail(-2, "conv: %d K slices for %d register-streamed K chunks", S, nchunks);
     const int lds = rlds_bytes<KT, WM, WK, NR, P>(pc * cch);
-    auto kern = conv_rkernel<KT, WM, WK, NR, P>;
-    static bool attr = false;   // opt in to the full 160 KiB once
-    if (!attr) {
-        OU_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds),
-                     "conv: LDS attribute");
-        attr = true;
-    }
-    const int mtiles = (d.m + 31) / 32;
-    const int cin_eff = d.cin * d.frame;
-    const int cin_pad = (cin_eff + kCinAlign - 1) / kCinAlign * kCinAlign;
-    const int64_t a_mt_stride = (int64_t)cin_pad * KT * 32;
+    constexpr auto kern = conv_rkernel<KT, WM, WK, NR, P>;
+    if (int rc = lds_opt_in<kern>(kMaxLds)) return rc;   // the full 160 KiB, whatever this launch needs
+    const auto [mtiles, cin_eff, cin_pad, a_mt_stride] = packed_geom(d.m, d.cin, d.frame, KT);
     dim3 grid((d.n_frames + R::BN - 1) / R::BN, (mtiles + WM - 1) / WM, d.batch);
     if (S > 1) {
         const int64_t need = (int64_t)grid.x * grid.y * grid.z * S * WM * NR * 16 * 64 * 4;
@@ -3363,43 +3433,31 @@ int launch_r(const ou_conv_desc& d, hipStream_t s)
 }
 
 template <int KT>
-int launch_rs(const ou_conv_desc& d, int shape, hipStream_t s)
+int launch_rs(const ou_conv_desc& d, const ou_tile_word& w, hipStream_t s)
 {
     if constexpr (KT == 1 || KT == 3 || KT == 5) {
-        switch (shape) {
-#define OU_RTILE_CASE(id, wm, wk, nr) \
-    case id: return d.prec == 1 ? launch_r<KT, wm, wk, nr, 1>(d, s) : launch_r<KT, wm, wk, nr, 2>(d, s);
+        switch (w.shape) {
+#define OU_RTILE_CASE(id, wm, wk, nr)                                             \
+    case id:                                                                      \
+        return d.prec == 1 ? launch_r<KT, wm, wk, nr, 1>(d, w.kslices, s)          \
+                           : launch_r<KT, wm, wk, nr, 2>(d, w.kslices, s);
             OU_RTILES(OU_RTILE_CASE)
 #undef OU_RTILE_CASE
         }
-        return ou_fail(-2, "conv: bad register-streamed tile %d", shape);
+        return ou_fail(-2, "conv: bad register-streamed tile %d", w.shape);
     } else {
-        (void)d, (void)shape, (void)s;
+        (void)d, (void)w, (void)s;
         return ou_fail(-2, "conv: no register-streamed kernel for kt %d", KT);
     }
 }
-
-// split-image shapes (tile bit 15): bits 0-7 = NR - 1 (32 NR frames per
-// workgroup), + 3: rows prefetched U - 0.5 chunks ahead instead of half a
-// chunk (more VGPRs: one wave per SIMD at NR 2 / 3)
-constexpr int kSsBit = 1 << 15;
-[[maybe_unused]] constexpr int kNumSTiles = 6;
 
 template <int KT, int NR, int DEEP>
 int launch_s1(const ou_conv_desc& d, hipStream_t s)
 {
     using S = SCfg<KT, NR, DEEP>;
-    auto kern = conv_skernel<KT, NR, DEEP>;
-    static bool attr = false;
-    if (!attr && S::LDS > 64 * 1024) {
-        OU_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS),
-                     "conv: LDS attribute");
-        attr = true;
-    }
-    const int mtiles = (d.m + 31) / 32;
-    const int cin_eff = d.cin * d.frame;
-    const int cin_pad = (cin_eff + kCinAlign - 1) / kCinAlign * kCinAlign;
-    const int64_t a_mt_stride = (int64_t)cin_pad * KT * 32;
+    constexpr auto kern = conv_skernel<KT, NR, DEEP>;
+    if (int rc = lds_opt_in<kern>(S::LDS)) return rc;
+    const auto [mtiles, cin_eff, cin_pad, a_mt_stride] = packed_geom(d.m, d.cin, d.frame, KT);
     dim3 grid((d.n_frames + 32 * NR - 1) / (32 * NR), mtiles, d.batch);
     hipLaunchKernelGGL(kern, grid, dim3(256), S::LDS, s, d, mtiles, a_mt_stride);
     return ou_check_launch("conv (split image)");
@@ -3424,138 +3482,115 @@ int launch_ss(const ou_conv_desc& d, int shape, hipStream_t s)
     }
 }
 
-// FIR shapes (tile bit 17): id, WM, WN, MR, NR (BM = 32 WM MR rows, BN = 32 WN NR frames)
-#define OU_FTILES(X) \
-    X(0, 2, 2, 1, 1) X(1, 4, 1, 1, 2) X(2, 2, 2, 2, 1) X(3, 1, 4, 2, 1) X(4, 2, 2, 1, 2) X(5, 4, 1, 2, 1) \
-    X(6, 2, 2, 2, 2) X(7, 4, 1, 1, 1)
-[[maybe_unused]] constexpr int kNumFTiles = 8;
-
-template <typename K>
-int fir_launch(K kern, int lds, dim3 grid, const ou_conv_desc& d, int mtiles, int64_t a_mt_stride, bool& attr,
-               hipStream_t s)
+template <auto Kern>
+int fir_launch(int lds, dim3 grid, const ou_conv_desc& d, int mtiles, int64_t a_mt_stride, hipStream_t s)
 {
-    if (!attr && lds > 64 * 1024) {
-        OU_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds),
-                     "conv: LDS attribute");
-        attr = true;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, d, mtiles, a_mt_stride);
+    if (int rc = lds_opt_in<Kern>(lds)) return rc;
+    hipLaunchKernelGGL(Kern, grid, dim3(256), lds, s, d, mtiles, a_mt_stride);
     return ou_check_launch("conv (FIR)");
 }
 
+template <int N>
+using int_c = std::integral_constant<int, N>;
+
 template <int R, int WM, int WN, int MR, int NR>
-int launch_f(const ou_conv_desc& d, hipStream_t s)
+int launch_f(const ou_conv_desc& d, const ou_tile_word& w, hipStream_t s)
 {
     using F = FCfg<R, WM, WN, MR, NR>;
-    static bool attr[4] = {false, false, false, false};   // (direction, precision) opted in to > 64 KiB
+    // the one place that turns d.prec into the kernels' template argument P
+    auto by_prec = [&](auto launch) { return d.prec == 1 ? launch(int_c<1>{}) : launch(int_c<2>{}); };
     if (d.fir == 1 || d.fir == 3) {   // down / st_conv: K = cin frame in chunks of 16 channels x R phases
-        const int mtiles = (d.m + 31) / 32;
-        const int64_t a_mt_stride = (int64_t)((d.cin * d.frame + kCinAlign - 1) / kCinAlign * kCinAlign) * 32;
-        const dim3 grid((d.n_frames + F::BN - 1) / F::BN, (mtiles + WM * MR - 1) / (WM * MR), d.batch);
+        const PackedGeom g = packed_geom(d.m, d.cin, d.frame, 1);
+        const dim3 grid((d.n_frames + F::BN - 1) / F::BN, (g.mtiles + WM * MR - 1) / (WM * MR), d.batch);
         const bool lean = !d.res1 && !d.res2 && !d.film;   // bias (+ split image) only: the lean epilogue
+        auto down = [&](auto st, auto ln, auto pd) {   // conv_fdkernel<..., P, ST, LEAN, PD>
+            return by_prec([&](auto p) {
+                return fir_launch<conv_fdkernel<R, WM, WN, MR, NR, decltype(p)::value, decltype(st)::value,
+                                                decltype(ln)::value, decltype(pd)::value>>(
+                    F::DLDS, grid, d, g.mtiles, g.a_mt_stride, s);
+            });
+        };
         if constexpr (R == 4 || R == 8) {
-            static bool sattr[4] = {false, false, false, false};
-            if (d.fir == 3 && lean)
-                return d.prec == 1 ? fir_launch(conv_fdkernel<R, WM, WN, MR, NR, 1, 1, 1>, F::DLDS, grid, d, mtiles,
-                                                a_mt_stride, sattr[0], s)
-                                   : fir_launch(conv_fdkernel<R, WM, WN, MR, NR, 2, 1, 1>, F::DLDS, grid, d, mtiles,
-                                                a_mt_stride, sattr[1], s);
+            if (d.fir == 3 && lean) return down(int_c<1>{}, int_c<1>{}, int_c<1>{});
             if (d.fir == 3)   // the st_convs' running sum: residuals in the epilogue
-                return d.prec == 1 ? fir_launch(conv_fdkernel<R, WM, WN, MR, NR, 1, 1, 0>, F::DLDS, grid, d, mtiles,
-                                                a_mt_stride, sattr[2], s)
-                                   : fir_launch(conv_fdkernel<R, WM, WN, MR, NR, 2, 1, 0>, F::DLDS, grid, d, mtiles,
-                                                a_mt_stride, sattr[3], s);
+                return down(int_c<1>{}, int_c<0>{}, int_c<1>{});
         }
         if (d.fir == 3) return ou_fail(-2, "conv: FIR mode 3 needs rate 4 or 8 chunks");
-        static bool lattr[4] = {false, false, false, false};
-        if (lean && (d.tile & kFirDeep))
-            return d.prec == 1 ? fir_launch(conv_fdkernel<R, WM, WN, MR, NR, 1, 0, 1, 2>, F::DLDS, grid, d, mtiles,
-                                            a_mt_stride, lattr[2], s)
-                               : fir_launch(conv_fdkernel<R, WM, WN, MR, NR, 2, 0, 1, 2>, F::DLDS, grid, d, mtiles,
-                                            a_mt_stride, lattr[3], s);
-        if (d.tile & kFirDeep) return ou_fail(-2, "conv: FIR tile bit 9 needs a down conv without residuals / FiLM");
-        if (lean)
-            return d.prec == 1
-                       ? fir_launch(conv_fdkernel<R, WM, WN, MR, NR, 1, 0, 1>, F::DLDS, grid, d, mtiles, a_mt_stride, lattr[0], s)
-                       : fir_launch(conv_fdkernel<R, WM, WN, MR, NR, 2, 0, 1>, F::DLDS, grid, d, mtiles, a_mt_stride, lattr[1], s);
-        return d.prec == 1
-                   ? fir_launch(conv_fdkernel<R, WM, WN, MR, NR, 1>, F::DLDS, grid, d, mtiles, a_mt_stride, attr[0], s)
-                   : fir_launch(conv_fdkernel<R, WM, WN, MR, NR, 2>, F::DLDS, grid, d, mtiles, a_mt_stride, attr[1], s);
+        if (lean && w.fir_deep) return down(int_c<0>{}, int_c<1>{}, int_c<2>{});
+        if (w.fir_deep) return ou_fail(-2, "conv: FIR tile bit 9 needs a down conv without residuals / FiLM");
+        if (lean) return down(int_c<0>{}, int_c<1>{}, int_c<1>{});
+        return down(int_c<0>{}, int_c<0>{}, int_c<1>{});
     }
     // up: K = cin in chunks of 32; P = 32 / R whole channels per packed m-tile
     const int mtiles = (d.m / R + F::CPT - 1) / F::CPT;
-    const int64_t a_mt_stride = (int64_t)((d.cin + kCinAlign - 1) / kCinAlign * kCinAlign) * 32;
+    const int64_t a_mt_stride = packed_geom(d.m, d.cin, 1, 1).a_mt_stride;
     const dim3 grid((d.n_frames + F::BN - 3) / (F::BN - 2), (mtiles + WM * MR - 1) / (WM * MR), d.batch);
-    if (d.tile & kFirDeep) {
-        if (d.tile & kFirEarly) return ou_fail(-2, "conv: FIR tile bits 8 and 9 together");
-        static bool pattr[2] = {false, false};
-        return d.prec == 1
-                   ? fir_launch(conv_fukernel<R, WM, WN, MR, NR, 1, 0, 2>, F::ULDS, grid, d, mtiles, a_mt_stride, pattr[0], s)
-                   : fir_launch(conv_fukernel<R, WM, WN, MR, NR, 2, 0, 2>, F::ULDS, grid, d, mtiles, a_mt_stride, pattr[1], s);
-    }
-    if (d.tile & kFirEarly) {
-        static bool eattr[2] = {false, false};
-        return d.prec == 1
-                   ? fir_launch(conv_fukernel<R, WM, WN, MR, NR, 1, 1>, F::ULDS, grid, d, mtiles, a_mt_stride, eattr[0], s)
-                   : fir_launch(conv_fukernel<R, WM, WN, MR, NR, 2, 1>, F::ULDS, grid, d, mtiles, a_mt_stride, eattr[1], s);
-    }
-    return d.prec == 1
-               ? fir_launch(conv_fukernel<R, WM, WN, MR, NR, 1>, F::ULDS, grid, d, mtiles, a_mt_stride, attr[2], s)
-               : fir_launch(conv_fukernel<R, WM, WN, MR, NR, 2>, F::ULDS, grid, d, mtiles, a_mt_stride, attr[3], s);
+    auto up = [&](auto early, auto pd) {   // conv_fukernel<..., P, EARLY, PD>
+        return by_prec([&](auto p) {
+            return fir_launch<conv_fukernel<R, WM, WN, MR, NR, decltype(p)::value, decltype(early)::value,
+                                            decltype(pd)::value>>(F::ULDS, grid, d, mtiles, a_mt_stride, s);
+        });
+    };
+    if (w.fir_deep && w.fir_early) return ou_fail(-2, "conv: FIR tile bits 8 and 9 together");
+    if (w.fir_deep) return up(int_c<0>{}, int_c<2>{});
+    if (w.fir_early) return up(int_c<1>{}, int_c<1>{});
+    return up(int_c<0>{}, int_c<1>{});
 }
 
 template <int R>
-int launch_fr(const ou_conv_desc& d, int shape, hipStream_t s)
+int launch_fr(const ou_conv_desc& d, const ou_tile_word& w, hipStream_t s)
 {
-    switch (shape) {
-#define OU_FTILE_CASE(id, wm, wn, mr, nr) case id: return launch_f<R, wm, wn, mr, nr>(d, s);
+    switch (w.shape) {
+#define OU_FTILE_CASE(id, wm, wn, mr, nr) case id: return launch_f<R, wm, wn, mr, nr>(d, w, s);
         OU_FTILES(OU_FTILE_CASE)
 #undef OU_FTILE_CASE
     }
-    return ou_fail(-2, "conv: bad FIR tile %d", shape);
+    return ou_fail(-2, "conv: bad FIR tile %d", w.shape);
 }
 
 template <int KT>
-int launch_kt(const ou_conv_desc& d, int tile, int tpw, bool ws, hipStream_t s)
+int launch_kt(const ou_conv_desc& d, const ou_tile_word& w, hipStream_t s)
 {
-    if (tile & kSsBit) return launch_ss<KT>(d, tile & 0xff, s);
-    if (tile & kRsBit) return launch_rs<KT>(d, tile & 0xff, s);
+    if (w.family == kSplitImage) return launch_ss<KT>(d, w.shape, s);
+    if (w.family == kRegStream) return launch_rs<KT>(d, w, s);
     if (d.prec == 1) {   // split-f16: one-tile workgroups (checked by ou_conv)
-        switch (tile) {
-#define OU_TILE_CASE(id, wm, wn, wk, mr, nr, big) case id: return launch_t<KT, wm, wn, wk, mr, nr, big, 1>(d, 1, s);
+        switch (w.shape) {
+#define OU_TILE_CASE(id, wm, wn, wk, mr, nr, big) \
+    case id: return launch_t<KT, wm, wn, wk, mr, nr, big, 1>(d, w.kslices, s);
             OU_TILES(OU_TILE_CASE)
 #undef OU_TILE_CASE
         }
-        return ou_fail(-2, "conv: bad tile %d", tile);
+        return ou_fail(-2, "conv: bad tile %d", w.shape);
     }
     if (d.prec == 2) {   // plain f16 (same layout and tiles as split-f16)
-        switch (tile) {
-#define OU_TILE_CASE(id, wm, wn, wk, mr, nr, big) case id: return launch_t<KT, wm, wn, wk, mr, nr, big, 2>(d, 1, s);
+        switch (w.shape) {
+#define OU_TILE_CASE(id, wm, wn, wk, mr, nr, big) \
+    case id: return launch_t<KT, wm, wn, wk, mr, nr, big, 2>(d, w.kslices, s);
             OU_TILES(OU_TILE_CASE)
 #undef OU_TILE_CASE
         }
-        return ou_fail(-2, "conv: bad tile %d", tile);
+        return ou_fail(-2, "conv: bad tile %d", w.shape);
     }
-    if (ws) {
-        switch (tile) {
+    if (w.family == kWarpSpec) {
+        switch (w.shape) {
 #define OU_TILE_CASE(id, wm, wn, wk, mr, nr, big) \
     case id:                                      \
         if constexpr (!big) return launch_w<KT, wm, wn, wk, mr, nr>(d, s); \
-        else return ou_fail(-2, "conv: tile %d has no warp-specialised form", tile);
+        else return ou_fail(-2, "conv: tile %d has no warp-specialised form", w.shape);
             OU_TILES(OU_TILE_CASE)
 #undef OU_TILE_CASE
         }
-        return ou_fail(-2, "conv: bad warp-specialised tile %d", tile);
+        return ou_fail(-2, "conv: bad warp-specialised tile %d", w.shape);
     }
-    switch (tile) {
+    switch (w.shape) {
 #define OU_TILE_CASE(id, wm, wn, wk, mr, nr, big)                                              \
     case id:                                                                                   \
-        return tpw > 1 ? launch_p<KT, wm, wn, wk, mr, nr, big>(d, tpw, s)                     \
-                       : launch_t<KT, wm, wn, wk, mr, nr, big>(d, tpw, s);
+        return w.tpw > 1 ? launch_p<KT, wm, wn, wk, mr, nr, big>(d, w.tpw, s)                 \
+                         : launch_t<KT, wm, wn, wk, mr, nr, big>(d, w.kslices, s);
         OU_TILES(OU_TILE_CASE)
 #undef OU_TILE_CASE
     }
-    return ou_fail(-2, "conv: bad tile %d", tile);
+    return ou_fail(-2, "conv: bad tile %d", w.shape);
 }
 
 // Static choice (used when the host has not autotuned the layer): the
@@ -3590,54 +3625,60 @@ int pick_tile(const ou_conv_desc& d)
 #define OU_CAT2(a, b) a##b
 #define OU_CAT(a, b) OU_CAT2(a, b)
 #if defined(OU_CONV_SPLIT_KT)
-int OU_CAT(ou_conv_launch_kt, OU_CONV_SPLIT_KT)(const ou_conv_desc& d, int tile, int tpw, bool ws, hipStream_t s)
+int OU_CAT(ou_conv_launch_kt, OU_CONV_SPLIT_KT)(const ou_conv_desc& d, const ou_tile_word& w, hipStream_t s)
 {
-    return launch_kt<OU_CONV_SPLIT_KT>(d, tile, tpw, ws, s);
+    return launch_kt<OU_CONV_SPLIT_KT>(d, w, s);
 }
-int OU_CAT(ou_conv_lds_kt, OU_CONV_SPLIT_KT)(int tile) { return lds_bytes_kt<OU_CONV_SPLIT_KT>(tile); }
+int OU_CAT(ou_conv_lds_kt, OU_CONV_SPLIT_KT)(const ou_tile_word& w) { return lds_bytes_kt<OU_CONV_SPLIT_KT>(w); }
 #elif defined(OU_CONV_SPLIT_FIR)   // the FIR kernels of one rate R (-DOU_CONV_SPLIT_FIR=R)
-int OU_CAT(ou_conv_launch_fir, OU_CONV_SPLIT_FIR)(const ou_conv_desc& d, int shape, hipStream_t s)
+int OU_CAT(ou_conv_launch_fir, OU_CONV_SPLIT_FIR)(const ou_conv_desc& d, const ou_tile_word& w, hipStream_t s)
 {
-    return launch_fr<OU_CONV_SPLIT_FIR>(d, shape, s);
+    return launch_fr<OU_CONV_SPLIT_FIR>(d, w, s);
 }
 #elif defined(OU_CONV_SPLIT_MAIN)
-#define OU_KT_DECL(K)                                                                           \
-    int ou_conv_launch_kt##K(const ou_conv_desc& d, int tile, int tpw, bool ws, hipStream_t s); \
-    int ou_conv_lds_kt##K(int tile);
+#define OU_KT_DECL(K)                                                                        \
+    int ou_conv_launch_kt##K(const ou_conv_desc& d, const ou_tile_word& w, hipStream_t s); \
+    int ou_conv_lds_kt##K(const ou_tile_word& w);
 OU_KT_DECL(1) OU_KT_DECL(3) OU_KT_DECL(4) OU_KT_DECL(5)
 #undef OU_KT_DECL
-#define OU_FIR_DECL(R) int ou_conv_launch_fir##R(const ou_conv_desc& d, int shape, hipStream_t s);
+#define OU_FIR_DECL(R) int ou_conv_launch_fir##R(const ou_conv_desc& d, const ou_tile_word& w, hipStream_t s);
 OU_FIR_DECL(2) OU_FIR_DECL(3) OU_FIR_DECL(4) OU_FIR_DECL(5) OU_FIR_DECL(8)
 #undef OU_FIR_DECL
 #define OU_LAUNCH_KT(K, ...) ou_conv_launch_kt##K(__VA_ARGS__)
-#define OU_LDS_KT(K, tile) ou_conv_lds_kt##K(tile)
+#define OU_LDS_KT(K, w) ou_conv_lds_kt##K(w)
 #define OU_LAUNCH_FIR(R, ...) ou_conv_launch_fir##R(__VA_ARGS__)
 #else
 #define OU_LAUNCH_KT(K, ...) launch_kt<K>(__VA_ARGS__)
-#define OU_LDS_KT(K, tile) lds_bytes_kt<K>(tile)
+#define OU_LDS_KT(K, w) lds_bytes_kt<K>(w)
 #define OU_LAUNCH_FIR(R, ...) launch_fr<R>(__VA_ARGS__)
 #endif
 
 #if !defined(OU_CONV_SPLIT_KT) && !defined(OU_CONV_SPLIT_FIR)
 namespace {
-int lds_bytes(int kt, int tile)
+int lds_bytes(int kt, const ou_tile_word& w)
 {
     switch (kt) {
-    case 1: return OU_LDS_KT(1, tile);
-    case 3: return OU_LDS_KT(3, tile);
-    case 4: return OU_LDS_KT(4, tile);
-    case 5: return OU_LDS_KT(5, tile);
+    case 1: return OU_LDS_KT(1, w);
+    case 3: return OU_LDS_KT(3, w);
+    case 4: return OU_LDS_KT(4, w);
+    case 5: return OU_LDS_KT(5, w);
     }
     return -1;
+}
+bool lds_fits(int kt, const ou_tile_word& w)
+{
+    const int lb = lds_bytes(kt, w);
+    return lb > 0 && lb <= kMaxLds;
 }
 
 // static choice for a precision: the split-f16 form lacks some shapes (LDS)
 int pick_tile_for(const ou_conv_desc& d)
 {
     const int t = pick_tile(d);
-    if (d.prec == 0 || lds_bytes(d.kt, t | kSplitBit) > 0) return t;
+    auto has_split_form = [&](int shape) { return lds_bytes(d.kt, decode_tile(shape | kSplitBit, d.kt, kQuery)) > 0; };
+    if (d.prec == 0 || has_split_form(t)) return t;
     for (int c : {11, 3, 6, 5, 1, 0, 10, 8, 2, 4, 7, 12})
-        if (lds_bytes(d.kt, c | kSplitBit) > 0) return c;
+        if (has_split_form(c)) return c;
     return t;
 }
 }  // namespace
@@ -3651,9 +3692,8 @@ extern "C" int ou_conv_chunk(int kt, int frame)
 extern "C" int64_t ou_conv_packed_size(int m, int cin_eff, int kt, int cc)
 {
     (void)cc;
-    const int64_t mtiles = (m + 31) / 32;
-    const int64_t cin_pad = (cin_eff + kCinAlign - 1) / kCinAlign * kCinAlign;
-    return mtiles * (cin_pad / 2) * kt * 64;
+    const PackedGeom g = packed_geom(m, cin_eff, 1, kt);
+    return g.mtiles * g.a_mt_stride;
 }
 
 // Packed order: [m-tile][p / 4][tap k][lane][p % 4] over channel pairs p;
@@ -3665,11 +3705,10 @@ extern "C" int ou_conv_pack(const float* w, int m, int cin_eff, int kt, int cc, 
     (void)cc;
     if (!w || !out || m <= 0 || cin_eff <= 0 || kt <= 0)
         return ou_fail(-1, "conv_pack: bad arguments");
-    const int mtiles = (m + 31) / 32;
-    const int cin_pad = (cin_eff + kCinAlign - 1) / kCinAlign * kCinAlign;
+    const PackedGeom g = packed_geom(m, cin_eff, 1, kt);
     int64_t o = 0;
-    for (int mt = 0; mt < mtiles; ++mt)
-        for (int pq = 0; pq < cin_pad / 8; ++pq)
+    for (int mt = 0; mt < g.mtiles; ++mt)
+        for (int pq = 0; pq < g.cin_pad / 8; ++pq)
             for (int k = 0; k < kt; ++k)
                 for (int lane = 0; lane < 64; ++lane)
                     for (int j = 0; j < 4; ++j) {
@@ -3680,17 +3719,20 @@ extern "C" int ou_conv_pack(const float* w, int m, int cin_eff, int kt, int cc, 
     return 0;
 }
 
-// Split-f16 packing (include/ouhip.h): [m-tile][8-pair group][hi | lo][tap]
-// [lane][8 halves] of a = w * 2^e; the same byte count per K chunk as the f32
-// packing, so the kernel's chunk addressing is unchanged.
-extern "C" int ou_conv_pack_split(const float* w, int m, int cin_eff, int kt, float* out, float* w_unscale)
+// Split-f16 packing (include/ouhip.h): [m-tile][16-channel group g][hi | lo]
+// [tap][lane][8 halves] of a = w * 2^e; the same byte count per K chunk as the
+// f32 packing, so the kernel's chunk addressing is unchanged.  channel(g, h, j)
+// is the channel that lane half h = lane >> 5 holds in half j of group g.
+namespace {
+template <typename ChannelOf>
+int pack_split(const char* who, const float* w, int m, int cin_eff, int kt, float* out, float* w_unscale,
+               ChannelOf channel)
 {
-    if (!w || !out || !w_unscale || m <= 0 || cin_eff <= 0 || kt <= 0)
-        return ou_fail(-1, "conv_pack_split: bad arguments");
+    if (!w || !out || !w_unscale || m <= 0 || cin_eff <= 0 || kt <= 0) return ou_fail(-1, "%s: bad arguments", who);
     const int64_t n = (int64_t)m * cin_eff * kt;
     float mx = 0.f;
     for (int64_t i = 0; i < n; ++i) {
-        if (!std::isfinite(w[i])) return ou_fail(-1, "conv_pack_split: non-finite weight at %lld", (long long)i);
+        if (!std::isfinite(w[i])) return ou_fail(-1, "%s: non-finite weight at %lld", who, (long long)i);
         mx = std::max(mx, std::fabs(w[i]));
     }
     int e = 0;
@@ -3700,17 +3742,16 @@ extern "C" int ou_conv_pack_split(const float* w, int m, int cin_eff, int kt, fl
         e = std::min(100, std::max(-100, 10 - ex));   // max|a| in [2^9, 2^10)
     }
     const float sc = std::ldexp(1.f, e);
-    const int mtiles = (m + 31) / 32;
-    const int cin_pad = (cin_eff + kCinAlign - 1) / kCinAlign * kCinAlign;
+    const PackedGeom pg = packed_geom(m, cin_eff, 1, kt);
     _Float16* o = (_Float16*)out;
-    for (int mt = 0; mt < mtiles; ++mt)
-        for (int g = 0; g < cin_pad / 16; ++g)
+    for (int mt = 0; mt < pg.mtiles; ++mt)
+        for (int g = 0; g < pg.cin_pad / 16; ++g)
             for (int part = 0; part < 2; ++part)
                 for (int k = 0; k < kt; ++k)
                     for (int lane = 0; lane < 64; ++lane)
                         for (int j = 0; j < 8; ++j) {
                             const int row = mt * 32 + (lane & 31);
-                            const int c = 2 * (8 * g + j) + (lane >> 5);
+                            const int c = channel(g, lane >> 5, j);
                             const float a =
                                 (row < m && c < cin_eff) ? w[((int64_t)row * cin_eff + c) * kt + k] * sc : 0.f;
                             const _Float16 hi = (_Float16)a;
@@ -3719,44 +3760,20 @@ extern "C" int ou_conv_pack_split(const float* w, int m, int cin_eff, int kt, fl
     *w_unscale = std::ldexp(1.f, kSplitShift - e);
     return 0;
 }
+}  // namespace
 
-// Natural-order split packing (include/ouhip.h): as ou_conv_pack_split with
-// lane l holding channel 16 g + 8 (l >> 5) + j of row l & 31 in half j.
+// the MFMA pair order of ou_conv_pack: channel 2 (8 g + j) + h
+extern "C" int ou_conv_pack_split(const float* w, int m, int cin_eff, int kt, float* out, float* w_unscale)
+{
+    return pack_split("conv_pack_split", w, m, cin_eff, kt, out, w_unscale,
+                      [](int g, int h, int j) { return 2 * (8 * g + j) + h; });
+}
+
+// natural order (split-image and FIR kernels): channel 16 g + 8 h + j
 extern "C" int ou_conv_pack_split_nat(const float* w, int m, int cin_eff, int kt, float* out, float* w_unscale)
 {
-    if (!w || !out || !w_unscale || m <= 0 || cin_eff <= 0 || kt <= 0)
-        return ou_fail(-1, "conv_pack_split_nat: bad arguments");
-    const int64_t n = (int64_t)m * cin_eff * kt;
-    float mx = 0.f;
-    for (int64_t i = 0; i < n; ++i) {
-        if (!std::isfinite(w[i])) return ou_fail(-1, "conv_pack_split_nat: non-finite weight at %lld", (long long)i);
-        mx = std::max(mx, std::fabs(w[i]));
-    }
-    int e = 0;
-    if (mx > 0.f) {
-        int ex = 0;
-        std::frexp(mx, &ex);
-        e = std::min(100, std::max(-100, 10 - ex));
-    }
-    const float sc = std::ldexp(1.f, e);
-    const int mtiles = (m + 31) / 32;
-    const int cin_pad = (cin_eff + kCinAlign - 1) / kCinAlign * kCinAlign;
-    _Float16* o = (_Float16*)out;
-    for (int mt = 0; mt < mtiles; ++mt)
-        for (int g = 0; g < cin_pad / 16; ++g)
-            for (int part = 0; part < 2; ++part)
-                for (int k = 0; k < kt; ++k)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int row = mt * 32 + (lane & 31);
-                            const int c = 16 * g + 8 * (lane >> 5) + j;
-                            const float a =
-                                (row < m && c < cin_eff) ? w[((int64_t)row * cin_eff + c) * kt + k] * sc : 0.f;
-                            const _Float16 hi = (_Float16)a;
-                            *o++ = part == 0 ? hi : (_Float16)((a - (float)hi) * 2048.f);
-                        }
-    *w_unscale = std::ldexp(1.f, kSplitShift - e);
-    return 0;
+    return pack_split("conv_pack_split_nat", w, m, cin_eff, kt, out, w_unscale,
+                      [](int g, int h, int j) { return 16 * g + 8 * h + j; });
 }
 
 extern "C" int ou_conv(const ou_conv_desc* dp, void* stream)
@@ -3781,7 +3798,12 @@ extern "C" int ou_conv(const ou_conv_desc* dp, void* stream)
             return ou_fail(-1, "conv: split-image output needs prec 1, rout 1, m %% 32 == 0, sy_rows >= out_len "
                                "(m %d rout %d rows %d out_len %d)", d.m, d.rout, d.sy_rows, d.out_len);
     }
-    if (d.fir || (d.tile >= 0 && (d.tile & kFirBit))) {   // FIR applied (bits 0-7: OU_FTILES shape)
+    hipStream_t s = (hipStream_t)stream;
+    // The order of the checks below decides which refusal a caller sees; keep it.
+    // tile -1 reads as an empty word here; each family then decodes its static choice.
+    int word = d.tile;
+    ou_tile_word w = decode_tile(word >= 0 ? word : 0, d.kt, kLaunch);
+    if (d.fir || w.family == kFir) {   // FIR applied
         // fir 3 (st_convs, no FIR): chunks of R = 8 (or 4) of the frame's phases
         const int R = d.fir == 1 ? d.frame : d.fir == 3 ? (d.frame % 8 == 0 ? 8 : 4) : (d.rout < 0 ? -d.rout : d.rout);
         if (d.fir < 1 || d.fir > 3 || (d.fir != 3 && !d.fir_taps) || (d.prec != 1 && d.prec != 2) || d.kt != 1 ||
@@ -3792,85 +3814,72 @@ extern "C" int ou_conv(const ou_conv_desc* dp, void* stream)
                                "(mode 3: a multiple of 4), cin %% 16 (down) / 32 (up) == 0 (cin %d frame %d rout %d kt %d)",
                            d.fir, d.cin, d.frame, d.rout, d.kt);
         if (!(d.w_unscale > 0.f)) return ou_fail(-1, "conv: FIR mode needs the w_unscale of ou_conv_pack_split_nat");
-        const int tile = d.tile >= 0 ? d.tile : (kFirBit | 2);
-        if (!(tile & kFirBit) || (tile & ~(kFirBit | kMajBit | kFirEarly | kFirDeep | 0xff)) || (tile & 0xff) >= kNumFTiles)
-            return ou_fail(-2, "conv: FIR mode needs a FIR tile (tile 0x%x)", d.tile);
+        if (word < 0) w = decode_tile(word = kFirBit | 2, d.kt, kLaunch);
+        if (w.family != kFir || w.fault) return ou_fail(-2, "conv: FIR mode needs a FIR tile (tile 0x%x)", d.tile);
         ou_conv_desc dd = d;   // the kernels read their order bit from the tile
-        dd.tile = tile;
-        hipStream_t fs = (hipStream_t)stream;
+        dd.tile = word;
         switch (R) {
-        case 2: return OU_LAUNCH_FIR(2, dd, tile & 0xff, fs);
-        case 3: return OU_LAUNCH_FIR(3, dd, tile & 0xff, fs);
-        case 4: return OU_LAUNCH_FIR(4, dd, tile & 0xff, fs);
-        case 5: return OU_LAUNCH_FIR(5, dd, tile & 0xff, fs);
-        case 8: return OU_LAUNCH_FIR(8, dd, tile & 0xff, fs);
+        case 2: return OU_LAUNCH_FIR(2, dd, w, s);
+        case 3: return OU_LAUNCH_FIR(3, dd, w, s);
+        case 4: return OU_LAUNCH_FIR(4, dd, w, s);
+        case 5: return OU_LAUNCH_FIR(5, dd, w, s);
+        case 8: return OU_LAUNCH_FIR(8, dd, w, s);
         }
         return ou_fail(-2, "conv: no FIR kernel for rate %d", R);
     }
-    if (d.xs || (d.tile >= 0 && (d.tile & kSsBit))) {   // split-image input (bits 0-7: NR - 1)
+    if (d.xs || w.family == kSplitImage) {   // split-image input
         // static choice: 64-frame workgroups while they still give one per CU
-        const int tile = d.tile >= 0 ? d.tile
-                         : kSsBit | ((int64_t)(d.n_frames + 63) / 64 * ((d.m + 31) / 32) * d.batch >= 256 ? 1 : 0);
-        if (!d.xs || !(tile & kSsBit) || (tile & ~(kSsBit | kMajBit | 0xff)) || (tile & 0xff) >= kNumSTiles)
+        if (word < 0)
+            w = decode_tile(word = kSsBit | ((int64_t)(d.n_frames + 63) / 64 * ((d.m + 31) / 32) * d.batch >= 256 ? 1 : 0),
+                            d.kt, kLaunch);
+        if (!d.xs || w.family != kSplitImage || w.fault)
             return ou_fail(-2, "conv: a split-image input needs a split-image tile (tile 0x%x)", d.tile);
         if (d.prec != 1 || d.cin % 32 || d.xs_rows < d.in_len || d.xs_shift < -100 ||
             d.xs_shift > 100 || (int64_t)(d.cin / 32) * d.xs_rows * 128 >= kSentinel)
             return ou_fail(-2, "conv: the split-image kernel needs prec 1, cin %% 32 == 0, xs_rows >= in_len, "
                                "(cin %d rows %d in_len %d)", d.cin, d.xs_rows, d.in_len);
         if (!(d.w_unscale > 0.f)) return ou_fail(-1, "conv: split-f16 needs the w_unscale of ou_conv_pack_split_nat");
-        hipStream_t ss = (hipStream_t)stream;
         ou_conv_desc dd = d;   // the kernel reads its order bit from the tile
-        dd.tile = tile;
+        dd.tile = word;
         switch (d.kt) {
-        case 1: return OU_LAUNCH_KT(1, dd, tile, 1, false, ss);
-        case 3: return OU_LAUNCH_KT(3, dd, tile, 1, false, ss);
-        case 5: return OU_LAUNCH_KT(5, dd, tile, 1, false, ss);
+        case 1: return OU_LAUNCH_KT(1, dd, w, s);
+        case 3: return OU_LAUNCH_KT(3, dd, w, s);
+        case 5: return OU_LAUNCH_KT(5, dd, w, s);
         }
         return ou_fail(-2, "conv: no split-image kernel for kt %d", d.kt);
     }
-    if (d.tile >= 0 && (d.tile & kRsBit)) {   // register-streamed kernel (bits 0-7: RTILES shape)
-        if ((d.tile & ~(kRsBit | kMajBit | 0x3ff | (3 << 12))) || (d.tile & 0xff) >= kNumRTiles)
-            return ou_fail(-2, "conv: bad register-streamed tile 0x%x", d.tile);
+    if (w.family == kRegStream) {   // the kernel reads its diagnostic mode, K slices and order from d.tile
+        if (w.fault) return ou_fail(-2, "conv: bad register-streamed tile 0x%x", d.tile);
         if ((d.prec != 1 && d.prec != 2) || d.cin % 16)
             return ou_fail(-2, "conv: the register-streamed kernel needs prec 1/2, cin %% 16 == 0");
         if (!(d.w_unscale > 0.f)) return ou_fail(-1, "conv: split-f16 needs the w_unscale of ou_conv_pack_split");
-        hipStream_t rs = (hipStream_t)stream;
-        const int t = d.tile & (0xff | kRsBit);   // bits 8-9 (diagnostics), 12-13 (K slices), 16 travel in d.tile
         switch (d.kt) {
-        case 1: return OU_LAUNCH_KT(1, d, t, 1, false, rs);
-        case 3: return OU_LAUNCH_KT(3, d, t, 1, false, rs);
-        case 5: return OU_LAUNCH_KT(5, d, t, 1, false, rs);
+        case 1: return OU_LAUNCH_KT(1, d, w, s);
+        case 3: return OU_LAUNCH_KT(3, d, w, s);
+        case 5: return OU_LAUNCH_KT(5, d, w, s);
         }
         return ou_fail(-2, "conv: no register-streamed kernel for kt %d", d.kt);
     }
-    // d.tile: bits 0-7 tile shape (kTiles), bits 8-9 log2(output tiles per
-    // workgroup: > 1 selects the persistent kernel, shapes without split-K),
-    // bit 10 the warp-specialised persistent kernel (shapes 0-12)
-    const int tile = d.tile >= 0 && (d.tile & 0xff) < kNumTiles ? (d.tile & 0xff) : pick_tile_for(d);
-    const bool ws = d.tile >= 0 && (d.tile & kWsBit);
-    const int tpw = d.tile >= 0 && !ws ? 1 << ((d.tile >> 8) & 3) : 1;
-    const int kslices = d.tile >= 0 ? 1 << ((d.tile >> 12) & 3) : 1;
-    if (kslices > 1 && (ws || tpw > 1))
-        return ou_fail(-2, "conv: K slices need the one-tile kernel (tile 0x%x)", d.tile);
-    if (d.tile >= 0 && (d.tile & kMajBit) && (ws || tpw > 1))
-        return ou_fail(-2, "conv: the m-major order needs the one-tile kernel (tile 0x%x)", d.tile);
+    // the plain families.  The kernel gets d.tile as it came, -1 included.
+    if (word < 0 || w.shape >= kNumTiles) w.shape = pick_tile_for(d);
+    const bool ws = w.family == kWarpSpec, multi = w.family != kPlain;   // multi: several tiles per workgroup
+    if (w.fault) return ou_fail(-2, "conv: %s (tile 0x%x)", w.fault, d.tile);
     if (ws && d.rout != 1) return ou_fail(-2, "conv: the warp-specialised kernel has no transposed (rout %d) form", d.rout);
     if (d.prec < 0 || d.prec > 2) return ou_fail(-1, "conv: bad precision %d", d.prec);
-    if (d.prec != 0 && (ws || tpw > 1))
+    if (d.prec != 0 && multi)
         return ou_fail(-2, "conv: the split-f16 form has one-tile workgroups only (tile 0x%x)", d.tile);
-    if (d.f0 != 0 && (ws || tpw > 1))
+    if (d.f0 != 0 && multi)
         return ou_fail(-2, "conv: a frame offset (f0 %d) needs the one-tile kernel (tile 0x%x)", d.f0, d.tile);
     if (d.prec != 0 && !(d.w_unscale > 0.f))
         return ou_fail(-1, "conv: split-f16 needs the w_unscale of ou_conv_pack_split");
-    const int lb = lds_bytes(d.kt, tile | (ws ? kWsBit : 0) | (d.prec != 0 ? kSplitBit : 0));
-    if (lb <= 0 || lb > kMaxLds)
-        return ou_fail(-2, "conv: tile %d (ws %d) needs %d B of LDS for kt=%d", tile, (int)ws, lb, d.kt);
-    hipStream_t s = (hipStream_t)stream;
+    w.split = d.prec != 0;   // the form whose LDS is asked for
+    if (!lds_fits(d.kt, w))
+        return ou_fail(-2, "conv: tile %d (ws %d) needs %d B of LDS for kt=%d", w.shape, (int)ws, lds_bytes(d.kt, w), d.kt);
     switch (d.kt) {
-    case 1: return OU_LAUNCH_KT(1, d, tile, tpw, ws, s);
-    case 3: return OU_LAUNCH_KT(3, d, tile, tpw, ws, s);
-    case 4: return OU_LAUNCH_KT(4, d, tile, tpw, ws, s);
-    case 5: return OU_LAUNCH_KT(5, d, tile, tpw, ws, s);
+    case 1: return OU_LAUNCH_KT(1, d, w, s);
+    case 3: return OU_LAUNCH_KT(3, d, w, s);
+    case 4: return OU_LAUNCH_KT(4, d, w, s);
+    case 5: return OU_LAUNCH_KT(5, d, w, s);
     }
     return ou_fail(-1, "conv: unsupported kt %d", d.kt);
 }
@@ -3883,10 +3892,12 @@ extern "C" int ou_conv_read_stamps(uint64_t* host, int n)
 #endif
 
 // LDS bytes a tile shape requests at a tap count, and the device's opt-in
-// per-workgroup LDS limit (diagnostics: tools/conv_bench.py --info)
+// per-workgroup LDS limit (diagnostics: tools/conv_bench.py --info).  Only the
+// shape, kWsBit and the split query bit of the word are looked at.
 extern "C" int ou_conv_lds_info(int kt, int tile, int* lds_request, int* device_optin_max)
 {
-    if (lds_request) *lds_request = lds_bytes(kt, tile & (0xff | kWsBit | kSplitBit));
+    if (lds_request)
+        *lds_request = lds_bytes(kt, decode_tile(tile & (OU_TILE_SHAPE_MASK | kWsBit | kSplitBit), kt, kQuery));
     int dev = 0, v = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -1;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess) return -1;
@@ -3896,35 +3907,11 @@ extern "C" int ou_conv_lds_info(int kt, int tile, int* lds_request, int* device_
 
 extern "C" int ou_conv_pick_tile(const ou_conv_desc* d) { return d ? pick_tile_for(*d) : -1; }
 extern "C" int ou_conv_num_tiles(void) { return kNumTiles; }
+// The register-streamed, split-image and FIR kernels check LDS and chunking at launch.
 extern "C" int ou_conv_tile_ok(int kt, int tile)
 {
-    if (tile & kFirBit)   // FIR applied (ou_conv_desc.fir): shape (+ m-major order); one tap
-        return !(tile & ~(kFirBit | kMajBit | kFirEarly | kFirDeep | 0xff)) && (tile & 0xff) < kNumFTiles && kt == 1;
-    if (tile & kSsBit)   // split-image input: shape = NR - 1 (+ m-major order)
-        return !(tile & ~(kSsBit | kMajBit | 0xff)) && (tile & 0xff) < kNumSTiles && (kt == 1 || kt == 3 || kt == 5);
-    if (tile & kRsBit)   // register-streamed: shape id (+ K slices, m-major order); LDS and chunks checked at launch
-        return !(tile & ~(kRsBit | kMajBit | 0xff | (3 << 12))) && (tile & 0xff) < kNumRTiles &&
-               (kt == 1 || kt == 3 || kt == 5);
-    if ((tile & kMajBit) && (tile & (kWsBit | (3 << 8)))) return 0;   // one-tile kernels only
-    tile &= ~kMajBit;
-    if (tile & kSplitBit) {   // split-f16 (d.prec = 1): one-tile workgroups, no other bits
-        if (tile & ~(kSplitBit | 0xff)) return 0;
-        if ((tile & 0xff) >= kNumTiles) return 0;
-        const int lb = lds_bytes(kt, tile);
-        return lb > 0 && lb <= kMaxLds;
-    }
-    if (tile & kWsBit) {   // warp-specialised: shapes without the 'big' chunking, no tpw bits
-        if (tile & ~(kWsBit | 0xff)) return 0;
-        const int t = tile & 0xff;
-        if (t >= kNumTiles || kTiles[t].big) return 0;
-        const int lb = lds_bytes(kt, tile);
-        return lb > 0 && lb <= kMaxLds;
-    }
-    if ((tile >> 8) & 3) {   // persistent: shapes without split-K only
-        const int t = tile & 0xff;
-        if (t >= kNumTiles || kTiles[t].wk != 1) return 0;
-    }
-    tile &= 0xff;
-    return tile >= 0 && tile < kNumTiles && lds_bytes(kt, tile) > 0 && lds_bytes(kt, tile) <= kMaxLds;
+    const ou_tile_word w = decode_tile(tile, kt, kQuery);
+    if (w.fault) return 0;
+    return w.family == kRegStream || w.family == kSplitImage || w.family == kFir || lds_fits(kt, w);
 }
 #endif  // !OU_CONV_SPLIT_KT

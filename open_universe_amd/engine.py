@@ -50,7 +50,6 @@ RANGE_SLOTS = 1024    # per-layer range-flag words after the engine's 4 status w
 MAX_SHIFT = 40        # staging exponents past this fall back to f32 operands
 _PREP_KSWS = (0, 0)   # (device float*, bytes): the engine's K-slice workspace
 KSWS_BYTES = 64 << 20
-RS_BIT = 1 << 14      # ConvDesc.tile bit: the register-streamed conv kernel (conv_rkernel)
 
 _REC = None   # set while a plan records (begin_record)
 # lane the recorder is on (plan lanes run concurrently) and the plan slot
@@ -94,13 +93,12 @@ _REC_DEVICE = None   # the recording engine's device (split-image buffers outsid
 # Anti-aliased rate-change convs (PReLU_Conv with use_antialiasing,
 # blocks.py:214-226) have two forms: the (2r+1)-tap binomial FIR folded into
 # 3-frame weights (any kernel; three times the reference's dense MACs) and the
-# FIR applied by conv_fdkernel / conv_fukernel (tile bit 17, ou_conv_desc.fir;
+# FIR applied by conv_fdkernel / conv_fukernel (TILE_FIR, ou_conv_desc.fir;
 # the reference's MACs).  OUHIP_FIR=auto (default) times both per layer and
 # records the faster, 1 always the FIR-applied form, 0 always the folded one.
 FIR_RATES = (2, 3, 4, 5, 8)
-FIR_BIT = 1 << 17
-FIR_EARLY = 1 << 8   # with FIR_BIT: the up kernel's residual / bias loads issued before its main loop
-FIR_DEEP = 1 << 9    # with FIR_BIT: two input chunks in flight per thread (lean down, up)
+# earlier names of the _lib tile constants, kept for callers outside the package
+RS_BIT, FIR_BIT, FIR_EARLY, FIR_DEEP = L.TILE_RS, L.TILE_FIR, L.TILE_FIR_EARLY, L.TILE_FIR_DEEP
 
 
 def fir_mode():
@@ -131,8 +129,8 @@ def end_record():
 # Split images (include/ouhip.h, ou_conv_desc.sy / xs).  A conv whose input
 # is the output of the conv recorded just before it on the same lane reads
 # that producer's split image -- the PReLU'd, scaled, f16 hi / lo operand the
-# producer's epilogue stores beside y -- through the split-image kernel (tile
-# bit 15), whose staging is then a plain copy.  The staging exponent of that
+# producer's epilogue stores beside y -- through the split-image kernel
+# (TILE_SS), whose staging is then a plain copy.  The staging exponent of that
 # consumer (ou_conv_desc.xs_shift) defaults to the fixed 2^-6 of the f32
 # staging path.
 SPLIT_SHIFT = 6
@@ -270,7 +268,7 @@ def split_hook(prog, op, d):
     if op == L.OP_CONV:
         d.xs_shift = shift
         d.w, d.w_unscale = d._w_nat
-        if d.tile >= 0 and not d.tile & L.SS_BIT:
+        if d.tile >= 0 and not d.tile & L.TILE_SS:
             d.tile = -1
 
 
@@ -328,7 +326,7 @@ class ConvW:
 @dataclass
 class FirW:
     """The FIR-applied form of an anti-aliased rate-change conv (ou_conv_desc.fir,
-    tile bit 17): unfolded weights (K = cin * rate down, cin up; one tap) in
+    TILE_FIR): unfolded weights (K = cin * rate down, cin up; one tap) in
     the kernels' order (include/ouhip.h), packed by ou_conv_pack_split_nat,
     and the (2 rate + 1)-tap binomial FIR on the device."""
     mode: int                # 1: FIR before a strided conv, 2: after a transposed conv, 3: no FIR (st_convs)
@@ -829,7 +827,7 @@ def rec_block(prog, bw: BlockW, h: Act, out: Act, tA: Act, tB: Act, film=0, film
 
 
 def fir_desc(d):
-    """The FIR-applied form (tile bit 17) of an anti-aliased rate-change
+    """The FIR-applied form (TILE_FIR) of an anti-aliased rate-change
     conv's folded descriptor ``d``: one tap, the unfolded weights and taps
     of its FirW, the same buffers, geometry and epilogue."""
     fw = d._fir
@@ -1032,9 +1030,9 @@ class ConvTuner:
     def fit_workspace(d, tile):
         """Drop the K-slice bits of a tile whose partial sums might not fit the
         workspace at this frame count (bound with generous tile padding)."""
-        S = 1 << ((tile >> 12) & 3)
+        S = 1 << ((tile & L.TILE_KS_MASK) >> L.TILE_KS_SHIFT)
         if S > 1 and S * (d.n_frames + 256) * (d.m + 256) * d.batch * 4 > d.ks_ws_bytes:
-            return tile & ~(3 << 12)
+            return tile & ~L.TILE_KS_MASK
         return tile
 
     def __call__(self, d):
@@ -1060,31 +1058,32 @@ class ConvTuner:
         best, best_ms = -1, float("inf")
         self.timed += 1
         # tile shape x log2(output tiles per workgroup); > 0 = persistent kernel
-        # (bit 10: the warp-specialised persistent kernel)
-        # (split-f16, bit 11 in the query only: one-tile workgroups)
-        # K slices (bits 12-13) for one-tile shapes when the engine has a
+        # (TILE_WS: the warp-specialised persistent kernel)
+        # (split-f16, TILE_SPLIT_QUERY in the query only: one-tile workgroups)
+        # K slices (TILE_KS_*) for one-tile shapes when the engine has a
         # workspace; ou_conv refuses slices beyond the chunk count or workspace
         # only where the grid is small (about 64 x 64 output tiles: under ~4
         # workgroups per CU); elsewhere slices only add traffic
         small = -(-d.n_frames // 64) * -(-d.m // 64) * d.batch <= 1024
-        ksl = (0, 1 << 12, 2 << 12, 3 << 12) if d.ks_ws and small else (0,)
+        ksl = tuple(k << L.TILE_KS_SHIFT for k in range(4)) if d.ks_ws and small else (0,)
         if d.fir:   # the FIR-applied rate-change kernels' shapes only
-            cands = [t | FIR_BIT for t in range(16) if lib.ou_conv_tile_ok(d.kt, t | FIR_BIT)]
-            if d.fir == 2:   # up: early epilogue loads (tile bit 8) or two chunks in flight (bit 9)
-                cands += [t | FIR_EARLY for t in cands] + [t | FIR_DEEP for t in cands]
+            cands = [t | L.TILE_FIR for t in range(16) if lib.ou_conv_tile_ok(d.kt, t | L.TILE_FIR)]
+            if d.fir == 2:   # up: early epilogue loads or two chunks in flight
+                cands += [t | L.TILE_FIR_EARLY for t in cands] + [t | L.TILE_FIR_DEEP for t in cands]
             elif d.fir == 1 and not (d.res1 or d.res2 or d.film):   # lean down: two chunks in flight
-                cands += [t | FIR_DEEP for t in cands]
+                cands += [t | L.TILE_FIR_DEEP for t in cands]
         elif d.xs:   # a split-image input: the split-image kernel's shapes only
-            cands = [t | L.SS_BIT for t in range(16) if lib.ou_conv_tile_ok(d.kt, t | L.SS_BIT)]
+            cands = [t | L.TILE_SS for t in range(16) if lib.ou_conv_tile_ok(d.kt, t | L.TILE_SS)]
         elif d.prec in (1, 2):
-            cands = [t | k for t in range(lib.ou_conv_num_tiles()) if lib.ou_conv_tile_ok(d.kt, t | (1 << 11))
-                     for k in ksl]
-            # register-streamed kernel (tile bit 14): whole input windows
+            cands = [t | k for t in range(lib.ou_conv_num_tiles())
+                     if lib.ou_conv_tile_ok(d.kt, t | L.TILE_SPLIT_QUERY) for k in ksl]
+            # register-streamed kernel: whole input windows
             # staged once; ou_conv refuses the shapes whose window exceeds LDS
             if d.cin % 16 == 0:
-                cands += [t | RS_BIT | k for t in range(16) if lib.ou_conv_tile_ok(d.kt, t | RS_BIT) for k in ksl]
+                cands += [t | L.TILE_RS | k for t in range(16) if lib.ou_conv_tile_ok(d.kt, t | L.TILE_RS) for k in ksl]
         else:
-            cands = [t | v for t in range(lib.ou_conv_num_tiles()) for v in (0, 1 << 8, 2 << 8, 1 << 10)
+            variants = (0, 1 << L.TILE_TPW_SHIFT, 2 << L.TILE_TPW_SHIFT, L.TILE_WS)
+            cands = [t | v for t in range(lib.ou_conv_num_tiles()) for v in variants
                      if lib.ou_conv_tile_ok(d.kt, t | v)]
             cands += [t | k for t in range(lib.ou_conv_num_tiles()) if lib.ou_conv_tile_ok(d.kt, t)
                       for k in ksl[1:]]
@@ -1123,7 +1122,9 @@ class ConvTuner:
             if log:   # diagnostics: name every candidate before it runs
                 with open(log, "a") as fh:
                     fh.write(f"m={d.m} cin={d.cin} frame={d.frame} kt={d.kt} n={d.n_frames} b={d.batch} "
-                             f"rout={d.rout} res1={bool(d.res1)} tile={t & 0xff} tpw={1 << ((t >> 8) & 3)} ws={t >> 10}\n")
+                             f"rout={d.rout} res1={bool(d.res1)} tile={t & L.TILE_SHAPE_MASK} "
+                             f"tpw={1 << ((t & L.TILE_TPW_MASK) >> L.TILE_TPW_SHIFT)} "
+                             f"ws={t // L.TILE_WS}\n")   # ws: the word from TILE_WS up
                     fh.flush()
                     os.fsync(fh.fileno())
             if lib.ou_conv(ctypes.byref(d), ctypes.c_void_p(stream)) != 0:
@@ -1218,7 +1219,7 @@ class Engine:
         # (range_owners[i]: a ConvW or FusedW), see plan.check / widen_ranges
         self.status = torch.zeros(4 + RANGE_SLOTS, dtype=torch.int32, device=dev)
         self.range_owners = []
-        # K-slice partial sums (ou_conv tile bits 12-13): ops of one lane run
+        # K-slice partial sums (ou_conv TILE_KS_*): ops of one lane run
         # one after another, so the convs of a lane share one buffer (one per
         # plan lane: conv_desc offsets by the recording lane)
         self.ks_ws = torch.empty(MAX_SLOTS * MAX_LANES * KSWS_BYTES // 4, dtype=torch.float32, device=dev)

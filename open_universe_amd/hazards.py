@@ -105,7 +105,7 @@ def _conv(d):
         R.append(_box(d.xs, d.xs_bstride, 0, d.batch, 1, 0, (d.cin // 32) * d.xs_rows * 128))
     if d.sy:
         W.append(_box(d.sy, d.sy_bstride, 0, d.batch, 1, 0, (d.m // 32) * d.sy_rows * 128))
-    if d.tile >= 0 and (d.tile >> 12) & 3 and not d.tile & (1 << 15):
+    if d.tile >= 0 and d.tile & L.TILE_KS_MASK and not d.tile & L.TILE_SS:
         W.append(_span(d.ks_ws, d.ks_ws_bytes))   # K-slice partial sums
     return R, W
 

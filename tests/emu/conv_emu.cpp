@@ -16,6 +16,10 @@ struct Geom {
     bool cm = false;   // channel-major output rows (ou_conv_desc.rout < 0)
 };
 
+// run()'s tile argument: a tile word, OU_TILE_SPLIT_QUERY for the split-f16
+// form (d.prec = 1) and with it this driver's own flag for f16 (d.prec = 2)
+constexpr int kEmuF16 = 1 << 30;
+
 static float* alloc(size_t n)
 {
     float* p = (float*)std::malloc(n * sizeof(float));   // exact size: ASan guards both ends
@@ -36,7 +40,7 @@ static int run(const Geom& g, int tile, bool chunk = false, int kslices = 1)
     const int64_t np = ou_conv_packed_size(m, cin_eff, g.kt, 0);
     float* w = alloc(np);
     float unscale = 1.f;
-    const bool split = tile & 2048;   // split-f16 form (d.prec = 1; 2 with bit 12: f16)
+    const bool split = tile & OU_TILE_SPLIT_QUERY;
     if (split)
         ou_conv_pack_split(wl.data(), m, cin_eff, g.kt, w, &unscale);
     else
@@ -59,12 +63,12 @@ static int run(const Geom& g, int tile, bool chunk = false, int kslices = 1)
     d.res1 = r1; d.r1_bstride = d.y_bstride; d.r1_cstride = d.y_cstride; d.s1 = 0.7f;
     d.film = fm; d.film_bstride = 2 * g.cout;
     d.res2 = r2; d.r2_bstride = d.y_bstride; d.r2_cstride = d.y_cstride; d.s2 = 0.5f;
-    d.tile = tile & ~(2048 | 4096);
-    d.prec = split ? ((tile & 4096) ? 2 : 1) : 0;
+    d.tile = tile & ~(OU_TILE_SPLIT_QUERY | kEmuF16);
+    d.prec = split ? ((tile & kEmuF16) ? 2 : 1) : 0;
     d.w_unscale = unscale;
-    float* ksws = nullptr;   // K-slice partial sums (register-streamed slices: tile bits 12-13)
+    float* ksws = nullptr;   // K-slice partial sums (register-streamed slices)
     if (kslices > 1) {
-        d.tile |= (kslices == 2 ? 1 : kslices == 4 ? 2 : 3) << 12;
+        d.tile |= (kslices == 2 ? 1 : kslices == 4 ? 2 : 3) << OU_TILE_KS_SHIFT;
         const int64_t n = (int64_t)((U + 31) / 32 + 2) * ((m + 31) / 32 + 4) * g.B * kslices * 4 * 1024;
         ksws = alloc((size_t)n);
         d.ks_ws = ksws;
@@ -111,7 +115,7 @@ int main(int argc, char** argv)
         {160, 96, 1, 3, 67, 1, 5, false, false, false, false},      // M = 800, partial m-groups
         {128, 256, 1, 3, 41, 2, 4, true, false, false, false, true},  // channel-major rows: 16-B epilogue
         {32, 64, 1, 3, 301, 1, 2, true, true, true, false, true},     // channel-major, 2 phases: 8-B epilogue
-        // register-streamed kernel (tile bit 14) shapes, run with its tiles
+        // register-streamed kernel (OU_TILE_RS) shapes, run with its tiles
         // only (kFirstRsGeom on): ragged 16-channel up
         // conv (3 steps < 4 K waves: the b31c724 fault), 1 step, deep k3 / k5,
         // frame views with and without the folded FIR, the conditioner's
@@ -136,16 +140,19 @@ int main(int argc, char** argv)
         const Geom& g = geoms[gi];
         for (int t = 0; t < std::max(ou_conv_num_tiles(), 16); ++t) {
             // 3: warp-specialised, 4: split-f16, 5: f16, 6 / 7: register-streamed
-            // kernel (tile bit 14) split-f16 / f16
+            // kernel (OU_TILE_RS) split-f16 / f16
             for (int tpw = 0; tpw < 8; ++tpw) {
                 if (tpw == 3 && g.rout != 1) continue;   // warp-specialised: plain convs only
                 if (tpw >= 6 && (t >= 16 || g.cin % 16)) continue;   // register-streamed: cin % 16 == 0
                 if (tpw < 6 && (rs_only || gi >= kFirstRsGeom || t >= ou_conv_num_tiles() || !ou_conv_tile_ok(g.kt, t)))
                     continue;
-                const int v = tpw >= 6 ? (2048 | (1 << 14)) : tpw >= 4 ? 2048 : tpw == 3 ? 1024 : tpw << 8;
-                if (!ou_conv_tile_ok(g.kt, tpw >= 6 ? (t | (1 << 14)) : (t | v))) continue;
+                const int v = tpw >= 6   ? (OU_TILE_SPLIT_QUERY | OU_TILE_RS)
+                              : tpw >= 4 ? OU_TILE_SPLIT_QUERY
+                              : tpw == 3 ? OU_TILE_WS
+                                         : tpw << OU_TILE_TPW_SHIFT;
+                if (!ou_conv_tile_ok(g.kt, tpw >= 6 ? (t | OU_TILE_RS) : (t | v))) continue;
                 if (std::getenv("OUHIP_EMU_VERBOSE")) std::fprintf(stderr, "geom %d tile %d tpw %d\n", gi, t, tpw);
-                const int rc = run(g, t | v | ((tpw == 5 || tpw == 7) ? 4096 : 0));
+                const int rc = run(g, t | v | ((tpw == 5 || tpw == 7) ? kEmuF16 : 0));
                 if (rc == -2 && tpw == 3) continue;   // warp-specialised form refused for this geometry
                 if (rc != 0 && tpw >= 6) continue;    // register-streamed form refused (window / LDS)
                 if (rc != 0) {
@@ -156,7 +163,7 @@ int main(int argc, char** argv)
                 nrs += tpw >= 6;
                 // the same tile on a frame range of the op (one-tile workgroups)
                 if (tpw == 0 || tpw >= 4) {
-                    const int rc2 = run(g, t | v | ((tpw == 5 || tpw == 7) ? 4096 : 0), true);
+                    const int rc2 = run(g, t | v | ((tpw == 5 || tpw == 7) ? kEmuF16 : 0), true);
                     if (rc2 != 0) {
                         std::fprintf(stderr, "geom %d tile %d tpw %d (frame range): ou_conv returned %d\n", gi, t, tpw, rc2);
                         return 2;

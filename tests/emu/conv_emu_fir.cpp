@@ -1,5 +1,5 @@
 // Numerics of the FIR-applied rate-change kernels on the CPU (fiber emulator,
-// OU_EMU_FIBERS; tile bit 17, ou_conv_desc.fir):
+// OU_EMU_FIBERS; OU_TILE_FIR, ou_conv_desc.fir):
 //   down: y[co][u] = bias + sum_{ci,ph} W[co][ci][ph] f[ci][u R + ph],
 //         f = FIR(prelu(x)) ('same', zero outside [0, T))     blocks.py:214-218
 //   up:   z[co][s] = sum_ci W[ci][co][s % R] prelu(x)[ci][s / R]  (s < T R),

@@ -56,7 +56,7 @@ int main(int argc, char** argv)
             if (!ou_conv_tile_ok(d.kt, t)) continue;
             for (int tpw = 0; tpw < 5; ++tpw) {   // 3: warp-specialised, 4: split-f16 (same weight bytes)
                 if (tpw == 3 && d.rout != 1) continue;   // warp-specialised: plain convs only
-                const int v = tpw == 4 ? 2048 : tpw == 3 ? 1024 : tpw << 8;
+                const int v = tpw == 4 ? OU_TILE_SPLIT_QUERY : tpw == 3 ? OU_TILE_WS : tpw << OU_TILE_TPW_SHIFT;
                 if (!ou_conv_tile_ok(d.kt, t | v)) continue;
                 if (std::getenv("OUHIP_EMU_VERBOSE"))
                     std::fprintf(stderr, "conv %zu (m %d cin %d frame %d kt %d n %d rout %d) tile %d tpw %d\n", ci, d.m,

@@ -3,7 +3,7 @@
 //     with ou_conv_desc.sy set stores, beside y, the split image of
 //     prelu(y) * 2^-s -- checked element by element (hi + lo 2^-11 within
 //     2^-21 relative of the f32 value, zero rows never written);
-//  2. the split-image kernel (tile bit 15) reading a host-built split image
+//  2. the split-image kernel (OU_TILE_SS) reading a host-built split image
 //     matches a double-precision evaluation of the ou_conv_desc formula for
 //     every NR shape, frame views, ragged lengths, residuals / FiLM and
 //     transposed (channel-major) outputs.
@@ -133,7 +133,7 @@ int main(int argc, char** argv)
             d.res2 = g.res2 ? r2.data() : nullptr; d.r2_bstride = d.y_bstride; d.r2_cstride = out_len; d.s2 = 0.5f;
             d.prec = 1; d.w_unscale = unscale;
             d.xs = img.data(); d.xs_bstride = (int64_t)(g.cin / 32) * rows * 128; d.xs_rows = rows; d.xs_shift = s;
-            d.tile = (1 << 15) | shape;
+            d.tile = OU_TILE_SS | shape;
             const int rc = ou_conv(&d, nullptr);
             if (rc != 0) {
                 std::printf("consumer geom %d shape %d: launch error %s\n", gi, shape, ouhip_detail::err_buf());
@@ -166,25 +166,26 @@ int main(int argc, char** argv)
         make_split(x, B, C, T, rows, 0.25f, 6, xin);
         std::vector<float> ksws(1 << 20);
         // tiles: chunked 11, chunked 11 in 2 K slices, register-streamed 0 and 0 in 2 K slices, split-image 1
-        const int tiles[] = {11, 11 | (1 << 12), (1 << 14) | 0, (1 << 14) | (1 << 12), (1 << 15) | 1};
+        const int ks2 = 1 << OU_TILE_KS_SHIFT;
+        const int tiles[] = {11, 11 | ks2, OU_TILE_RS | 0, OU_TILE_RS | ks2, OU_TILE_SS | 1};
         for (int tile : tiles) {
             std::vector<float> y((size_t)B * C * T, 1e30f);
             std::vector<uint16_t> img((size_t)B * (C / 32) * rows * 64, 0x7e00);
             ou_conv_desc d{};
             d.x = x.data(); d.x_bstride = (int64_t)C * T; d.x_cstride = T;
             d.cin = C; d.in_len = T; d.frame = 1; d.slope = 0.25f;
-            d.w = (tile & (1 << 15)) ? pkn.data() : pk.data(); d.w_unscale = (tile & (1 << 15)) ? unn : un;
+            d.w = (tile & OU_TILE_SS) ? pkn.data() : pk.data(); d.w_unscale = (tile & OU_TILE_SS) ? unn : un;
             d.m = C; d.kt = kt; d.pad = 1; d.n_frames = T; d.batch = B;
             d.y = y.data(); d.y_bstride = (int64_t)C * T; d.y_cstride = T; d.rout = 1; d.out_len = T;
             d.valid_len = T - 3; d.res1 = r1.data(); d.r1_bstride = (int64_t)C * T; d.r1_cstride = T; d.s1 = 0.7f;
             d.prec = 1; d.tile = tile; d.ks_ws = ksws.data(); d.ks_ws_bytes = (int64_t)ksws.size() * 4;
-            if (tile & (1 << 15)) {
+            if (tile & OU_TILE_SS) {
                 d.xs = xin.data(); d.xs_bstride = (int64_t)(C / 32) * rows * 128; d.xs_rows = rows; d.xs_shift = 6;
             }
             d.sy = img.data(); d.sy_bstride = (int64_t)(C / 32) * rows * 128; d.sy_rows = rows; d.sy_shift = s;
             d.sy_slope = yslope;
             const int rc = ou_conv(&d, nullptr);
-            if (rc == -2 && (tile & (3 << 12))) continue;   // more K slices than K chunks
+            if (rc == -2 && (tile & OU_TILE_KS_MASK)) continue;   // more K slices than K chunks
             if (rc != 0) {
                 std::printf("producer tile 0x%x: launch error %s\n", tile, ouhip_detail::err_buf());
                 ++bad;

@@ -59,6 +59,22 @@ def test_struct_layouts_match_c():
             assert int(got[f"{cname}.{fname}"]) == getattr(py, fname).offset, (cname, fname)
 
 
+def test_tile_constants_match_c():
+    """Every OU_TILE_* field constant of the header has its mirror _lib.TILE_*."""
+    names = re.findall(r"^#define (OU_TILE_[A-Z0-9_]+)\b", open(HEADER).read(), re.M)
+    assert len(names) == 15 and len(set(names)) == 15, names
+    lines = ['#include <stdio.h>', f'#include "{HEADER}"', "int main(void){"]
+    lines += [f'printf("{n} %d\\n", (int)({n}));' for n in names]
+    lines.append("return 0;}")
+    with tempfile.TemporaryDirectory() as d:
+        src, exe = os.path.join(d, "t.c"), os.path.join(d, "t")
+        open(src, "w").write("\n".join(lines))
+        subprocess.check_call(["gcc", "-std=c99", "-o", exe, src])
+        got = dict(line.split() for line in subprocess.check_output([exe]).decode().splitlines())
+    assert {n[3:]: int(v) for n, v in got.items()} == {n[3:]: getattr(L, n[3:]) for n in names}
+    assert sorted(n for n in dir(L) if n.startswith("TILE_")) == sorted(n[3:] for n in names)
+
+
 def test_conv_pack_layout():
     """Packed order: [mtile][pair // 4][tap][lane][pair % 4], lane -> (row =
     lane & 31, channel = 2 * pair + (lane >> 5)); channels zero-padded to a

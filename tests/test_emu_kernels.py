@@ -35,7 +35,7 @@ ASAN = ("-O0", "-g0", "-fsanitize=address", "-fno-omit-frame-pointer")
 
 def test_conv_tiles_in_bounds(tmp_path):
     """Every ou_conv tile of the chunked kernel, and every register-streamed
-    (conv_rkernel, tile bit 14) shape on ragged / 1-step / deep / frame-view /
+    (conv_rkernel, OU_TILE_RS) shape on ragged / 1-step / deep / frame-view /
     K-chunked (st_conv) geometries, split-f16 and f16."""
     exe = str(tmp_path / "conv_emu")
     _build("conv_emu.cpp", exe, *ASAN)
@@ -189,7 +189,7 @@ def test_block_values_match_reference(tmp_path):
 
 def test_split_image_values_match_reference(tmp_path):
     """Fiber emulation of the split-image path, under AddressSanitizer: the
-    consumer kernel (tile bit 15) against a double-precision evaluation at
+    consumer kernel (OU_TILE_SS) against a double-precision evaluation at
     every NR shape (k1/k3/k5, frame views at rates 4 and 5, a transposed
     channel-major output, a one-chunk layer whose other waves run zero
     chunks), and the split image every producer kernel family stores
@@ -205,7 +205,7 @@ def test_split_image_values_match_reference(tmp_path):
 
 
 def test_fir_values_match_reference(tmp_path):
-    """Fiber emulation of the FIR-applied rate-change kernels (tile bit 17,
+    """Fiber emulation of the FIR-applied rate-change kernels (OU_TILE_FIR,
     conv_fdkernel / conv_fukernel), under AddressSanitizer: every OU_FTILES
     shape (and the m-major order), split-f16 and f16, down (FIR before the
     strided conv; ragged lengths, FiLM, the split-image output) and up (FIR

@@ -15,6 +15,9 @@ from open_universe_amd import engine as E
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+SPLIT = L.TILE_SPLIT_QUERY   # ou_conv_tile_ok: the shape's split-f16 form
+# one-tile, persistent x2 / x4, warp-specialised, split-f16
+VARIANTS = (0, 1 << L.TILE_TPW_SHIFT, 2 << L.TILE_TPW_SHIFT, L.TILE_WS, SPLIT)
 _KSWS = []
 
 
@@ -72,16 +75,16 @@ def test_conv_every_tile(geom):
     for t in range(lib.ou_conv_num_tiles()):
         if not lib.ou_conv_tile_ok(kt, t):
             continue
-        # one-tile, persistent x2 / x4, warp-specialised; split-f16 (query bit 11)
-        for v in (0, 1 << 8, 2 << 8, 1 << 10, 1 << 11):
+        # one-tile, persistent x2 / x4, warp-specialised; split-f16 (the query bit)
+        for v in VARIANTS:
             if not lib.ou_conv_tile_ok(kt, t | v):
                 continue
             y = E.new_act(B, cout, U, DEV)
             ra = E.Act(res.to(DEV)) if with_res else None
-            d = E.conv_desc(cws[1 if v == 1 << 11 else 0], xa, y, res1=ra, s1=0.7, n_frames=U)
-            d.tile = t | (v & ~(1 << 11))
+            d = E.conv_desc(cws[1 if v == SPLIT else 0], xa, y, res1=ra, s1=0.7, n_frames=U)
+            d.tile = t | (v & ~SPLIT)
             rc = lib.ou_conv(ctypes.byref(d), ctypes.c_void_p(stream))
-            if rc == -2 and v == 1 << 10:
+            if rc == -2 and v == L.TILE_WS:
                 continue   # warp-specialised form refused for this geometry (single K chunk, rout > 1)
             assert rc == 0
             torch.cuda.synchronize()
@@ -90,13 +93,13 @@ def test_conv_every_tile(geom):
                 bad.append((t, v, err))
         # K slices (two launches: partial sums, then reduce + epilogue), both precisions
         for prec, sl in ((0, 1), (1, 2), (1, 3)):
-            if not lib.ou_conv_tile_ok(kt, t | (prec << 11)):
+            if not lib.ou_conv_tile_ok(kt, t | (SPLIT if prec else 0)):
                 continue
             y = E.new_act(B, cout, U, DEV)
             ra = E.Act(res.to(DEV)) if with_res else None
             d = E.conv_desc(cws[prec], xa, y, res1=ra, s1=0.7, n_frames=U)
             d.ks_ws, d.ks_ws_bytes = _ksws().data_ptr(), _ksws().numel() * 4
-            d.tile = t | (sl << 12)
+            d.tile = t | (sl << L.TILE_KS_SHIFT)
             rc = lib.ou_conv(ctypes.byref(d), ctypes.c_void_p(stream))
             if rc == -2:
                 continue   # more K slices than chunks, or workspace too small
@@ -135,15 +138,15 @@ def test_conv_full_epilogue_every_tile(geom):
     stream = torch.cuda.current_stream().cuda_stream
     bad = []
     for t in range(lib.ou_conv_num_tiles()):
-        for v in (0, 1 << 8, 2 << 8, 1 << 10, 1 << 11):
+        for v in VARIANTS:
             if not lib.ou_conv_tile_ok(kt, t | v):
                 continue
             y = E.new_act(B, cout, U, DEV)
-            d = E.conv_desc(cws[1 if v == 1 << 11 else 0], xa, y, res1=r1a, s1=0.7, film=fd.data_ptr(),
+            d = E.conv_desc(cws[1 if v == SPLIT else 0], xa, y, res1=r1a, s1=0.7, film=fd.data_ptr(),
                             film_bs=2 * cout, res2=r2a, s2=0.5, n_frames=U, valid_len=valid)
-            d.tile = t | (v & ~(1 << 11))
+            d.tile = t | (v & ~SPLIT)
             rc = lib.ou_conv(ctypes.byref(d), ctypes.c_void_p(stream))
-            if rc == -2 and v == 1 << 10:
+            if rc == -2 and v == L.TILE_WS:
                 continue   # warp-specialised form refused for this geometry (single K chunk, rout > 1)
             assert rc == 0
             torch.cuda.synchronize()
@@ -199,9 +202,9 @@ def test_conv_f16_every_tile(geom):
     ws = torch.empty(E.KSWS_BYTES // 4, dtype=torch.float32, device=DEV)   # K-slice partial sums
     bad, n = [], 0
     for t in range(lib.ou_conv_num_tiles()):
-        if not lib.ou_conv_tile_ok(kt, t | (1 << 11)):
+        if not lib.ou_conv_tile_ok(kt, t | SPLIT):
             continue
-        for ks in (0, 1 << 12, 2 << 12):   # one workgroup per tile, 2 and 4 K slices
+        for ks in (0, 1 << L.TILE_KS_SHIFT, 2 << L.TILE_KS_SHIFT):   # one workgroup per tile, 2 and 4 K slices
             y = E.new_act(B, cout, U, DEV)
             d = E.conv_desc(cw, xa, y, n_frames=U)
             d.ks_ws, d.ks_ws_bytes = ws.data_ptr(), E.KSWS_BYTES
@@ -218,7 +221,7 @@ def test_conv_f16_every_tile(geom):
     assert n and not bad, bad
 
 
-RS_BIT = 1 << 14
+RS_BIT = L.TILE_RS
 # (m, cin, frame, kt, rout, T, batch): deep same-convs, the GRU input
 # projection, a transposed (rout) up-conv, frame-view (strided) down-convs
 # with and without the folded FIR, rows past M and a ragged short clip
@@ -247,7 +250,7 @@ RS_GEOMS = [
 
 @pytest.mark.parametrize("geom", RS_GEOMS, ids=[str(g) for g in RS_GEOMS])
 def test_conv_register_streamed_every_shape(geom):
-    """The register-streamed kernel (tile bit 14), every shape, split-f16 and
+    """The register-streamed kernel (OU_TILE_RS), every shape, split-f16 and
     f16, with the full epilogue (bias, residual 1, FiLM, residual 2, valid_len,
     the rout pixel shuffle, the frame view): equal to the chunked kernel on the
     same packed weights up to f32 summation order."""
@@ -302,7 +305,7 @@ def test_conv_register_streamed_every_shape(geom):
                 bad.append((prec, t, err))
             # K slices (K-chunked windows only; refused where chunks < slices)
             for k in (1, 2, 3):
-                rc, y = run(t | RS_BIT | (k << 12))
+                rc, y = run(t | RS_BIT | (k << L.TILE_KS_SHIFT))
                 if rc == -2:
                     continue
                 assert rc == 0, lib.ou_last_error()

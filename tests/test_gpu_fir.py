@@ -1,4 +1,4 @@
-"""The FIR-applied rate-change kernels (tile bit 17, ou_conv_desc.fir:
+"""The FIR-applied rate-change kernels (OU_TILE_FIR, ou_conv_desc.fir:
 conv_fdkernel / conv_fukernel) on the GPU, through the C ABI.
 
 PReLU_Conv with use_antialiasing (reference networks/universe/blocks.py:214-226)
@@ -88,10 +88,10 @@ def test_fir_every_tile(direction, r, prec):
     lib = L.load()
     n = 0
     # up: early epilogue loads / two chunks in flight; down (bias only here): two chunks in flight
-    early = (0, E.FIR_EARLY, E.FIR_DEEP) if direction == "up" else (0, E.FIR_DEEP)
+    early = (0, L.TILE_FIR_EARLY, L.TILE_FIR_DEEP) if direction == "up" else (0, L.TILE_FIR_DEEP)
     for shape in range(16):
-        for mm in [m | e for m in (0, L.MAJ_BIT) for e in early]:
-            t = E.FIR_BIT | shape | mm
+        for mm in [m | e for m in (0, L.TILE_MMAJOR) for e in early]:
+            t = L.TILE_FIR | shape | mm
             if not lib.ou_conv_tile_ok(1, t):
                 continue
             y.t.fill_(float("nan"))
@@ -173,8 +173,8 @@ def test_st_conv_fir3_every_tile(rt, cin, cout):
         f = E.fir_desc(d)
         assert f.fir == 3
         for shape in range(16):
-            for mm in (0, L.MAJ_BIT):
-                t = E.FIR_BIT | shape | mm
+            for mm in (0, L.TILE_MMAJOR):
+                t = L.TILE_FIR | shape | mm
                 if not lib.ou_conv_tile_ok(1, t):
                     continue
                 y.t.fill_(float("nan"))

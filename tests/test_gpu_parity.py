@@ -54,7 +54,7 @@ def _run_conv(cw, x, out_shape, form="folded", **kw):
     xa = E.Act(x.to(DEV).contiguous())
     y = E.new_act(*out_shape, DEV)
     d = E.conv_desc(cw, xa, y, **kw)
-    if form == "fir":   # the FIR-applied kernels (tile bit 17) instead of the folded weights
+    if form == "fir":   # the FIR-applied kernels (OU_TILE_FIR) instead of the folded weights
         assert cw.fir is not None
         d = E.fir_desc(d)
     L.run_now(L.OP_CONV, d, torch.cuda.current_stream().cuda_stream)

@@ -1,5 +1,5 @@
 """Split images on the GPU (include/ouhip.h, ou_conv_desc.sy / xs): the
-split-image kernel (tile bit 15) against a torch fp32 reference of the same
+split-image kernel (OU_TILE_SS) against a torch fp32 reference of the same
 convolution for every shape (plain / frame view / 1x1 / transposed,
 ragged lengths, batch 2, residual epilogue), the split image a producer's
 epilogue stores against its restatement, and the per-layer staging exponent
@@ -88,21 +88,21 @@ def test_split_image_kernel_every_shape(geom):
     lib = L.load()
     stream = torch.cuda.current_stream().cuda_stream
     for shape in range(6):
-        for mj in (0, 1 << 16):
+        for mj in (0, L.TILE_MMAJOR):
             y = E.new_act(B, cout, U * rout, DEV)
             y.t.fill_(float("nan"))
             ra = E.Act(res.to(DEV)) if with_res else None
             d = E.conv_desc(cw, xa, y, res1=ra, s1=0.7, n_frames=U)
             d.xs, d.xs_bstride, d.xs_rows, d.xs_shift = img.data_ptr(), img.numel() * 2 // B, T + 2, 6
             d.w, d.w_unscale = cw.w_nat.data_ptr(), cw.w_unscale_nat
-            d.tile = L.SS_BIT | shape | mj
+            d.tile = L.TILE_SS | shape | mj
             assert lib.ou_conv(ctypes.byref(d), ctypes.c_void_p(stream)) == 0, lib.ou_last_error()
             torch.cuda.synchronize()
             err = ((y.t.cpu().double() - ref).norm() / ref.norm()).item()
             assert err < 1e-5, (shape, mj, err)
 
 
-@pytest.mark.parametrize("tile", [11, 11 | (1 << 12), E.RS_BIT | 2, L.SS_BIT | 1])
+@pytest.mark.parametrize("tile", [11, 11 | (1 << L.TILE_KS_SHIFT), L.TILE_RS | 2, L.TILE_SS | 1])
 def test_producer_stores_split_image(tile):
     """A conv with ou_conv_desc.sy stores prelu_{a'}(y) 2^-s beside y (the
     chunked, K-sliced, register-streamed and split-image kernels alike)."""
@@ -118,7 +118,7 @@ def test_producer_stores_split_image(tile):
     d = E.conv_desc(cw, x, y)
     ws = torch.empty(E.KSWS_BYTES // 4, dtype=torch.float32, device=DEV)   # K-slice partial sums
     d.ks_ws, d.ks_ws_bytes = ws.data_ptr(), E.KSWS_BYTES
-    if tile & L.SS_BIT:
+    if tile & L.TILE_SS:
         img = split_image(x.t, 0.25, 6)
         d.xs, d.xs_bstride, d.xs_rows, d.xs_shift = img.data_ptr(), img.numel() * 2 // B, T, 6
         d.w, d.w_unscale = cw.w_nat.data_ptr(), cw.w_unscale_nat
@@ -149,7 +149,7 @@ def test_staging_exponent_and_range_codes():
     st = torch.zeros(4, dtype=torch.int32, device=DEV)
     lib = L.load()
     stream = torch.cuda.current_stream().cuda_stream
-    for shift, tile in ((6, 11), (10, 11), (6, E.RS_BIT | 2), (10, E.RS_BIT | 2)):
+    for shift, tile in ((6, 11), (10, 11), (6, L.TILE_RS | 2), (10, L.TILE_RS | 2)):
         st.zero_()
         d = E.conv_desc(cw, xa, y)
         d.status, d.xs_shift, d.tile = st.data_ptr(), shift, tile

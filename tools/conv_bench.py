@@ -83,7 +83,7 @@ def split_image(x, slope, shift, rows=None):
 
 
 def split_variant(d, keep, shift=6):
-    """The same layer reading a split image of its input (tile bit 15)."""
+    """The same layer reading a split image of its input (OU_TILE_SS)."""
     cw, x = keep[0], keep[1]
     img = split_image(x.t, cw.slope, shift)
     ds = L.ConvDesc.from_buffer_copy(d)
@@ -153,7 +153,7 @@ def main():
                     help="with --split, a library built with -DOU_SK_STAMPS: per-wave phase cycles of the best "
                          "split-image tile")
     ap.add_argument("--split", action="store_true",
-                    help="also time the split-image kernel (tile bit 15) on a split image of the input, check its "
+                    help="also time the split-image kernel (OU_TILE_SS) on a split image of the input, check its "
                          "output against the best tile's, and re-time the best tile storing a split image (sy)")
     a = ap.parse_args()
     dev = "cuda:0"
@@ -164,15 +164,15 @@ def main():
         d, keep = make(name, dev)
         if d.prec == 1:
             tiles = [a.tile] if a.tile is not None else [t | k for t in range(lib.ou_conv_num_tiles())
-                                                          if lib.ou_conv_tile_ok(d.kt, t | (1 << 11))
-                                                          for k in (0, 1 << 12, 2 << 12, 3 << 12)]
+                                                          if lib.ou_conv_tile_ok(d.kt, t | L.TILE_SPLIT_QUERY)
+                                                          for k in (s << L.TILE_KS_SHIFT for s in range(4))]
             if a.tile is None and d.cin % 16 == 0:   # register-streamed kernel
-                tiles += [t | E.RS_BIT for t in range(16) if lib.ou_conv_tile_ok(d.kt, t | E.RS_BIT)]
+                tiles += [t | L.TILE_RS for t in range(16) if lib.ou_conv_tile_ok(d.kt, t | L.TILE_RS)]
                 if a.rdiag:
-                    tiles += [t | v for t in tiles if t & E.RS_BIT for v in (1 << 8, 2 << 8, 3 << 8)]
+                    tiles += [t | v for t in tiles if t & L.TILE_RS for v in (m << L.TILE_RS_DIAG_SHIFT for m in (1, 2, 3))]
         else:
             tiles = [a.tile] if a.tile is not None else [t | v for t in range(lib.ou_conv_num_tiles())
-                                                          for v in (0, 1 << 8, 2 << 8, 1 << 10)
+                                                          for v in (0, 1 << L.TILE_TPW_SHIFT, 2 << L.TILE_TPW_SHIFT, L.TILE_WS)
                                                           if lib.ou_conv_tile_ok(d.kt, t | v)]
         res = []
         for t in tiles:
@@ -182,10 +182,12 @@ def main():
         res.sort()
         fl = d._flops
         def nm(t):
-            if t & E.RS_BIT:
-                return f"r{t & 0xff}" + ("" if not (t >> 8) & 3 else f"d{(t >> 8) & 3}")
-            return (f"t{t & 0xff}" + ("w" if (t >> 10) & 1 else (f"p{1 << ((t >> 8) & 3)}" if (t >> 8) & 3 else ""))
-                    + (f"k{1 << (t >> 12)}" if t >> 12 else ""))
+            if t & L.TILE_RS:
+                diag = (t & L.TILE_RS_DIAG_MASK) >> L.TILE_RS_DIAG_SHIFT
+                return f"r{t & L.TILE_SHAPE_MASK}" + (f"d{diag}" if diag else "")
+            tpw, ks = (t & L.TILE_TPW_MASK) >> L.TILE_TPW_SHIFT, (t & L.TILE_KS_MASK) >> L.TILE_KS_SHIFT
+            return (f"t{t & L.TILE_SHAPE_MASK}" + ("w" if t & L.TILE_WS else (f"p{1 << tpw}" if tpw else ""))
+                    + (f"k{1 << ks}" if ks else ""))
         line = "  ".join(f"{nm(t)}:{ms * 1e3:.1f}us" for ms, t in res[:40 if a.rdiag else 12])
         print(f"{name:5s} {fl / 1e9:6.2f} GFLOP  best {nm(res[0][1])} {res[0][0] * 1e3:.1f} us "
               f"{fl / res[0][0] / 1e9:.1f} TF/s | {line}", flush=True)
@@ -200,10 +202,10 @@ def main():
             ds, img = split_variant(d, keep)
             sres = []
             for t in range(6):
-                for mj in (0, 1 << 16):
-                    ms = time_tile(ds, L.SS_BIT | t | mj, a.reps, stream)
+                for mj in (0, L.TILE_MMAJOR):
+                    ms = time_tile(ds, L.TILE_SS | t | mj, a.reps, stream)
                     if ms is not None:
-                        sres.append((ms, L.SS_BIT | t | mj))
+                        sres.append((ms, L.TILE_SS | t | mj))
             sres.sort()
             ds.tile = sres[0][1]
             y.fill_(float("nan"))
@@ -238,7 +240,7 @@ def main():
                           f"wave lifetime {life:.2f} us; starts "
                           f"0..{(st[:, :, 6].max() - t0) / 100:.2f} us, last end {(st[:, :, 7].max() - t0) / 100:.2f} us",
                           flush=True)
-            sl = "  ".join(f"s{t & 0xff}{'m' if t & (1 << 16) else ''}:{ms * 1e3:.1f}us" for ms, t in sres)
+            sl = "  ".join(f"s{t & L.TILE_SHAPE_MASK}{'m' if t & L.TILE_MMAJOR else ''}:{ms * 1e3:.1f}us" for ms, t in sres)
             print(f"      split image: best {sres[0][0] * 1e3:.1f} us {fl / sres[0][0] / 1e9:.1f} TF/s "
                   f"(rel diff vs best tile {err:.2e}) | {sl}" +
                   (f" | best tile storing sy: {t_sy * 1e3:.1f} us" if t_sy else ""), flush=True)
@@ -270,7 +272,7 @@ def main():
             st = np.frombuffer(buf, dtype=np.uint64).reshape(4096, 8).astype(np.float64)
             st = st[st.sum(1) > 0]
             names = ("prologue", "load_issue", "mfma", "store", "barrier", "epilogue")
-            if (res[0][1] if a.tile is None else a.tile) & E.RS_BIT:
+            if (res[0][1] if a.tile is None else a.tile) & L.TILE_RS:
                 names = ("ring_issue", "staging", "barrier", "mfma", "reduce", "epilogue")
             mean = st.mean(0)
             rt0, rt1 = st[:, 6], st[:, 7]

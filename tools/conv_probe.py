@@ -34,7 +34,7 @@ def main():
         rc = lib.ou_conv(ctypes.byref(d), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         torch.cuda.synchronize()
         err = ((y.t.cpu() - ref).norm() / ref.norm()).item()
-        print(f"tile {t & 0xff} tpw {1 << (t >> 8)}: rc {rc} lds {req.value} (optin max {opt.value}) rel err {err:.3g}",
+        print(f"tile {t & L.TILE_SHAPE_MASK} tpw {1 << ((t & L.TILE_TPW_MASK) >> L.TILE_TPW_SHIFT)}: rc {rc} lds {req.value} (optin max {opt.value}) rel err {err:.3g}",
               flush=True)
 
 

@@ -6,7 +6,7 @@
 For every score-network rate-change conv of the config (the shapes its plan
 records: B items, level lengths of the config's clip), the tuner times every
 tile of the folded form (3-frame weights, the other kernels) and of the
-FIR-applied form (tile bit 17); prints ms per launch, the reference's
+FIR-applied form (TILE_FIR); prints ms per launch, the reference's
 algorithmic TF/s and GB/s (engine.conv_desc's _flops / _bytes) and the ratio.
 Random weights and inputs (timing does not depend on values).
 """

@@ -31,6 +31,7 @@ import sys
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, HERE)
+from open_universe_amd import _lib as L  # noqa: E402  (the tile constants)
 
 CONV_KERNELS = ("conv_kernel", "conv_rkernel", "conv_skernel", "conv_pkernel", "conv_wkernel", "conv_rreduce",
                 "conv_fdkernel", "conv_fukernel", "block_kernel")
@@ -40,7 +41,7 @@ PEAK = {0: 157.3e12, 1: 2516.6e12 / 3, 2: 2516.6e12}
 
 def n_dispatch(row):
     if row["kind_name"] == "conv":
-        return 2 if (row["tile"] >> 12) & 3 else 1
+        return 2 if row["tile"] & L.TILE_KS_MASK else 1
     return 1
 
 
