@@ -831,6 +831,54 @@ int ou_window_gather(const float* x, int64_t x_rstride, int rows, int64_t T, int
 int ou_overlap_add(const float* w, int64_t w_bstride, int64_t T, int window, int overlap, int64_t first,
                    int count, const float* fade, float* y, void* stream);
 
+/* Pooled windows (ou_pool.hip): the windows of several clips, each longer than
+ * W, share the groups of one (B, W) plan.  Clip c of `n_clips` has n_c windows
+ * with the starts above; the slot list is every (c, i) in clip order, i
+ * ascending, N = sum n_c slots; a group is `count` consecutive slots from slot
+ * `first`, a slot index >= N meaning slot N - 1.  The calls keep no state and
+ * allocate nothing: each works out its slots from the host array `clips`
+ * (device pointers inside) and launches once per 32 slots.
+ *
+ * ou_pool_slots: the arithmetic alone (host; no HIP call): *n_slots = N.
+ *
+ * ou_pool_gather: for b < count, slot first + b = (c, i): mix[b mix_bstride + j]
+ * = x_c[start_i + j], j < W, and for r < noise_rows: nz[r nz_rstride +
+ * b nz_bstride + j] = noise_c[r noise_rstride_c + start_i + j], j < noise_win
+ * (the plan's padded window length; a clip's noise rows hold
+ * start(n_c - 1) + noise_win values).  One launch per 32 slots copies MIX and
+ * every NZ row.  x and, when noise_rows > 0, noise of every clip are read; y is
+ * not.
+ *
+ * ou_pool_overlap_add: crossfades the outputs of slots [first, first + count)
+ * below N (slot first + b at w + b w_bstride, W values) into their clips' y.
+ * Sample t of a clip belongs to window own = min(t / H, n_c - 1).  The owner
+ * stores the finished value, (0 + (1 - f) v_prev) + f v inside its fade-in and
+ * 0 + 1 v elsewhere, taking the first term from the previous slot when that is
+ * part of this call and from y[t] otherwise; a window whose successor is not
+ * part of this call stores 0 + (1 - f) v over the successor's fade-in for the
+ * next call to finish.  So the groups must run in slot order from first = 0,
+ * after which every sample of every y has been stored (y needs no clearing)
+ * with the bits ou_overlap_add gives clip by clip, wherever the group
+ * boundaries fall.  y of every clip is written; x and noise are not read.
+ *
+ * All refuse, on the host: a null list, n_clips < 1, any T <= W, O outside
+ * [0, W / 2]; the two launching calls also first outside [0, N), count < 1,
+ * null pointers they use, strides smaller than a row, noise_rstride <
+ * start(n_c - 1) + noise_win when noise_rows > 0, two clips whose y ranges
+ * overlap (overlap_add), and a missing fade table when O > 0 (overlap_add). */
+typedef struct ou_pool_clip {      /* host struct, device pointers */
+    const float* x;                /* the clip, T samples */
+    const float* noise;            /* rows of noise_rstride floats; may be null when noise_rows == 0 */
+    float* y;                      /* the result, T samples */
+    int64_t T, noise_rstride;
+} ou_pool_clip;
+int ou_pool_slots(const int64_t* T, int n_clips, int window, int overlap, int64_t* n_slots);
+int ou_pool_gather(const ou_pool_clip* clips, int n_clips, int window, int overlap, int64_t first, int count,
+                   int noise_rows, int64_t noise_win, float* mix, int64_t mix_bstride,
+                   float* nz, int64_t nz_rstride, int64_t nz_bstride, void* stream);
+int ou_pool_overlap_add(const ou_pool_clip* clips, int n_clips, int window, int overlap, int64_t first, int count,
+                        const float* w, int64_t w_bstride, const float* fade, void* stream);
+
 /* Windowed enhance through a loaded bundle: W and the group size B are the
  * bundle's own (mix.length, mix.batch); x and out are device pointers of n
  * floats, n > W (n <= W is ou_model_enhance's case and refused).  Windows

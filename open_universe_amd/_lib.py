@@ -164,6 +164,11 @@ class BundleMeta(ctypes.Structure):
                 ("json", c_char_p), ("json_bytes", c_int64), ("arch", c_char * 16)]
 
 
+class PoolClip(ctypes.Structure):
+    """ou_pool_clip: one clip of a pooled windowed enhance (device pointers)."""
+    _fields_ = [("x", fp), ("noise", fp), ("y", fp), ("T", c_int64), ("noise_rstride", c_int64)]
+
+
 OP_STRUCT = {
     OP_CONV: ConvDesc, OP_GRU: GruDesc, OP_EMBED: EmbedDesc, OP_HEAD: HeadDesc,
     OP_NORMALIZE: NormArgs, OP_INV_RMS: RmsArgs, OP_RMS: RmsArgs, OP_POWER: PowerArgs,
@@ -251,6 +256,11 @@ EXPORTS = {
     "ou_window_gather": (c_int, [fp, c_int64, c_int, c_int64, c_int, c_int, c_int64, c_int, c_int64, fp, c_int64,
                                  c_int64, c_void_p]),
     "ou_overlap_add": (c_int, [fp, c_int64, c_int64, c_int, c_int, c_int64, c_int, fp, fp, c_void_p]),
+    "ou_pool_slots": (c_int, [POINTER(c_int64), c_int, c_int, c_int, POINTER(c_int64)]),
+    "ou_pool_gather": (c_int, [POINTER(PoolClip), c_int, c_int, c_int, c_int64, c_int, c_int, c_int64, fp, c_int64,
+                               fp, c_int64, c_int64, c_void_p]),
+    "ou_pool_overlap_add": (c_int, [POINTER(PoolClip), c_int, c_int, c_int, c_int64, c_int, fp, c_int64, fp,
+                                    c_void_p]),
     "ou_model_long_noise": (c_int64, [c_void_p, c_int64, c_int, POINTER(c_int64)]),
     "ou_model_enhance_long_noise": (c_int, [c_void_p, fp, c_int64, c_int, fp, fp, c_void_p]),
     "ou_model_enhance_long": (c_int, [c_void_p, fp, c_int64, c_int, fp, c_uint64, c_uint64, fp, c_void_p]),

@@ -12,17 +12,23 @@ Differences: audio is resampled to ``model.fs`` and back on the GPU
 ``--chunk`` with ``--streams`` clips in flight (Universe.enhance_many); with
 ``--window SECONDS`` (and ``--overlap``, ``--window-batch``) a file longer than
 the window goes through ``Universe.enhance_long`` instead, so that every long
-file uses one plan shape whatever its length.  Under
-torchrun (WORLD_SIZE > 1) each rank enhances its share of the files on
-``cuda:LOCAL_RANK`` (``sharding.shard_utterances``, balanced by file size) --
-no collectives.
+file uses one plan shape whatever its length.  With ``--window-pool`` as well,
+every run of consecutive long files inside a ``--chunk`` group goes through one
+``Universe.enhance_long_many`` call, their windows sharing the groups of that
+plan.  Under torchrun (WORLD_SIZE > 1) each rank enhances its share of the
+files on ``cuda:LOCAL_RANK`` (``sharding.shard_utterances``, balanced by file
+size) -- no collectives.
 
 Noise: as in the reference (bin/enhance.py:71-73,147-148,173-189), one
 generator seeded with ``--seed`` draws every file's noise in the order
 ``rglob`` lists the files (suffix matched case-sensitively).  A rank draws and
 discards the noise of the files other ranks enhance (``Universe.skip_noise``,
 from the file headers), so every file gets the same noise -- and the same
-output -- whatever the world size.
+output -- whatever the world size.  Under ``--window-pool`` every file still
+gets the same noise, but its output depends on which files share a group of
+windows with it, and so on which files a rank has: those outputs are not
+promised bit-equal across world sizes (they agree to the end-to-end
+tolerance).  Without the flag they still are.
 
     python -m open_universe_amd.bin.enhance noisy/ enhanced/ --model exp/ckpt.ckpt
     python -m torch.distributed.run --nproc-per-node 8 -m open_universe_amd.bin.enhance noisy/ out/ --model ...
@@ -70,6 +76,9 @@ def build_parser():
                         help="crossfaded overlap of two windows, at most half the window (with --window)")
     parser.add_argument("--window-batch", type=int, default=8, metavar="N",
                         help="windows per replay (with --window)")
+    parser.add_argument("--window-pool", action="store_true",
+                        help="consecutive long files of a --chunk group share their replays "
+                             "(Universe.enhance_long_many; with --window)")
     return parser
 
 
@@ -90,6 +99,8 @@ def window_settings(args, fs):
 def main(argv=None):
     parser = build_parser()
     args, _ = parser.parse_known_args(argv)
+    if args.window_pool and args.window is None:
+        raise SystemExit("--window-pool pools the windows of long files: it needs --window SECONDS")
 
     rank, local, world = dist_env()
     device = args.device or f"cuda:{local}"
@@ -160,11 +171,17 @@ def main(argv=None):
         with torch.no_grad():
             xs = [resample(a.to(device), fs, model.fs) for a, fs in loaded]
             # in file order (the noise order): a long file on its own through
-            # enhance_long, every run of other files the existing way
+            # enhance_long (with --window-pool every run of long files through
+            # one enhance_long_many), every run of other files the existing way
             ys, j = [None] * len(xs), 0
             while j < len(xs):
                 k = j + 1
-                if is_long(xs[j]):
+                if is_long(xs[j]) and args.window_pool:
+                    while k < len(xs) and is_long(xs[k]):
+                        k += 1
+                    ys[j:k] = model.enhance_long_many(xs[j:k], pre_noise=lambda q, j=j: skip(skip_before[i + j + q]),
+                                                      **long_kw)
+                elif is_long(xs[j]):
                     skip(skip_before[i + j])
                     ys[j] = model.enhance_long(xs[j], **long_kw)
                 elif many_ok:

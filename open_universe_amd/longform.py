@@ -34,6 +34,22 @@ Result.  ``y[t] = sum_i weight_i(t) out_i[t - start_i]`` with ``out_i`` what
 (windows ``[g B, g B + B)``, ``B = min(batch, n)``) on its slice of the noise,
 through the normal finish (crop, ``keep_rms`` against the window's own input
 RMS, peak division).
+
+Pooled windows (``Universe.enhance_long_many``, csrc/ou_pool.hip).  Clips
+``c = 0 .. C - 1`` of lengths ``T_c > W`` have ``n_c`` windows each, with the
+starts above.  The slot list is ``[(c, i) for c in order for i in
+range(n_c)]``, ``N = sum n_c``; ``B = min(batch, N)`` and group ``g`` holds
+the slots ``[g B, g B + B)``, a slot index ``>= N`` meaning slot ``N - 1`` (the
+last window of the last clip, whose output is dropped).  The noise is per clip
+and unchanged: clip ``c`` draws its ``n_noise`` tensors ``(1, 1, L_c)`` in
+clip order -- the draws of consecutive ``enhance_long`` calls -- and window
+``(c, i)`` uses ``G_c[k, 0, start_{c,i} : start_{c,i} + Tp]``.  The result is
+``y_c[t] = sum_i weight_{c,i}(t) out_{c,i}[t - start_{c,i}]`` with the weights
+above and ``out_{c,i}`` what ``enhance()`` returns for that window in its slot
+of its group, evaluated per sample in float32 as ``(0 + w_{i-1} v_{i-1}) +
+w_i v_i``, each product and sum rounded -- so ``y_c`` depends on the ``out``
+values alone, not on where the group boundaries fall.  For one clip this is
+``enhance_long`` itself: the same slots, the same replays, the same bits.
 """
 import numpy as np
 
@@ -121,3 +137,64 @@ def overlap_add(outs, T, W, O, dtype=np.float64):
         m = min(W, int(T) - s)
         y[s:s + m] += (w[i, s:s + m].astype(dtype) * outs[i, :m].astype(dtype)).astype(dtype)
     return y
+
+
+def pool(Ts, W, O, batch):
+    """(B, slots) of the pooled windows of clips of lengths ``Ts``, each longer
+    than ``W``: ``slots = [(c, i) for c in order for i in range(n_c)]`` and
+    ``B = min(batch, N)``; group ``g`` holds the slots ``[g B, g B + B)``."""
+    slots = []
+    for c, T in enumerate(Ts):
+        T, W, O = check(T, W, O)
+        if T <= W:
+            raise ValueError(f"clip {c} has {T} samples: only clips longer than the window ({W}) take slots")
+        slots.extend((c, i) for i in range(n_windows(T, W, O)))
+    if not slots:
+        raise ValueError("no clips")
+    return max(1, min(int(batch), len(slots))), slots
+
+
+def overlap_add_pooled(outs, Ts, W, O, batch):
+    """The pooled result evaluated as ou_pool_overlap_add does, group by group
+    in float32, for outs (N, W) in slot order: the list of ``y_c``.
+
+    Sample ``t`` of a clip belongs to window ``own = min(t // H, n_c - 1)``.
+    In the call for a group, the owner's slot stores the finished sample --
+    ``0 + 1 v`` outside its fade-in, ``(0 + (1 - f) v_{i-1}) + f v_i`` inside
+    it, the first term taken from slot ``b - 1`` when that is in the group and
+    from ``y[t]`` (left by the group before) otherwise; a slot whose successor
+    window is not in the group stores ``0 + (1 - f) v`` over the successor's
+    fade-in; nothing else is written.  Every ``y_c`` starts as NaN, and no
+    sample may be stored twice by one group."""
+    B, slots = pool(Ts, W, O, batch)
+    N, H, f32 = len(slots), int(W) - int(O), np.float32
+    outs = np.asarray(outs, dtype=f32)
+    tab = fade_table(O)
+    ys = [np.full(int(T), np.nan, dtype=f32) for T in Ts]
+    j = np.arange(int(W))
+    for first in range(0, N, B):
+        stop = min(first + B, N)
+        stores = []   # applied after the group's reads: the threads of one call do not see each other's stores
+        for b in range(first, stop):
+            c, i = slots[b]
+            n = n_windows(Ts[c], W, O)
+            t = start(i, Ts[c], W, O) + j
+            own = np.minimum(t // H, n - 1)
+            v = outs[b]
+            prev_in, next_in = i > 0 and b > first, i + 1 < n and b + 1 < stop
+            u = t - i * H
+            plain = (own == i) & ((i == 0) | (u >= O))
+            stores.append((c, t[plain], f32(0) + f32(1) * v[plain]))
+            fin = (own == i) & ~plain
+            if fin.any():
+                acc = f32(0) + tab[1][u[fin]] * outs[b - 1][u[fin] + H] if prev_in else ys[c][t[fin]]
+                stores.append((c, t[fin], acc + tab[0][u[fin]] * v[fin]))
+            out = own == i + 1
+            if not next_in and out.any():
+                stores.append((c, t[out], f32(0) + tab[1][t[out] - (i + 1) * H] * v[out]))
+        seen = [np.zeros(int(T), dtype=bool) for T in Ts]
+        for c, t, val in stores:
+            assert not seen[c][t].any(), "one group stored a sample twice"
+            seen[c][t] = True
+            ys[c][t] = val.astype(f32)
+    return ys

@@ -454,6 +454,125 @@ class Universe(nn.Module):
         out = torch.stack(outs)
         return out[0] if mix.ndim == 1 else out if mix.ndim == 2 else out[:, None, :]
 
+    def enhance_long_many(self, mixes, window: int, overlap: int, batch: int = 8, n_steps: Optional[int] = None,
+                          epsilon: Optional[float] = None, rng: Optional[torch.Generator] = None,
+                          keep_rms: Optional[bool] = False, pre_noise=None, **unsupported):
+        """Windowed enhance of a sequence of clips whose windows share their
+        replays (opt-in; longform.py "Pooled windows").
+        Each element of ``mixes`` is (T,), (b, T) or (b, 1, T) as
+        ``enhance_long`` takes them, rows being consecutive clips; lengths may
+        differ.  The windows of every clip longer than ``window`` form one slot
+        list in clip order, and groups of ``min(batch, N)`` slots -- whatever
+        clips they come from -- run through the (batch, window) plan of
+        ``enhance_long``: a folder of clips pays for part-empty slots once, in
+        the last group, not once per clip.  Returns the list of outputs, each
+        of its element's shape.
+
+        The noise is that of consecutive ``enhance_long`` calls: in list order
+        ``pre_noise(i)``, if given, runs and then element ``i`` draws its
+        global noise (``noise_shapes`` / ``skip_noise`` apply unchanged).  An
+        element with ``T <= window`` runs ``enhance()`` right there, as
+        ``enhance_long`` would, and takes no slot.  A clip's result depends on
+        the outputs of its own windows alone, not on where the group
+        boundaries fall -- but a window's output depends, at rounding level,
+        on the other windows of its group.  For a single clip this is
+        ``enhance_long(clip, ...)`` bit for bit.  The refusals are those of
+        ``enhance_long``, made before anything is drawn or launched.
+
+        Device memory beyond the plan's arena, all of it held until the call
+        returns: every pooled clip (T_c floats), its output (T_c floats) and
+        its global noise, ``n_steps * L_c`` floats with ``L_c = start_{n_c-1}
+        + Tp`` -- ``(2 + n_steps) T_c`` floats per clip, summed over the
+        clips of the call."""
+        from ... import longform
+
+        for k, v in unsupported.items():
+            if k in ("target", "fake_score_snr", "use_aux_signal", "ensemble", "ensemble_stat", "warm_start"):
+                if v is not None and v is not False and not (k == "ensemble_stat" and v == "median"):
+                    raise NotImplementedError(f"enhance_long_many does not support {k}")
+            else:
+                raise TypeError(f"enhance_long_many() got an unexpected keyword argument {k!r}")
+        mixes = list(mixes)
+        W = O = None
+        for mix in mixes:   # before anything is drawn or launched
+            if mix.ndim > 3 or mix.ndim < 1 or (mix.ndim == 3 and mix.shape[1] != 1):
+                raise ValueError("The input should be (T,), (B, T) or (B, 1, T)")
+            _, W, O = longform.check(mix.shape[-1], window, overlap)
+        if int(batch) < 1:
+            raise ValueError(f"batch must be at least 1, got {batch}")
+        if not mixes:
+            return []
+        if epsilon is None:
+            epsilon = self.diff_kwargs.epsilon
+        if n_steps is None:
+            n_steps = self.diff_kwargs.n_steps
+        eng = self._get_engine()
+        dev = eng.device
+        n_noise = int(n_steps)
+        Tp = W + self.tot_ds - W % self.tot_ds
+        outs = [None] * len(mixes)
+        xs, Gs, owner = [], [], []   # the pooled clips, their global noise, the element each belongs to
+        for i, mix in enumerate(mixes):
+            T = mix.shape[-1]
+            if pre_noise is not None:
+                pre_noise(i)
+            if T <= W:
+                outs[i] = self.enhance(mix, n_steps=n_steps, epsilon=epsilon, rng=rng, keep_rms=keep_rms)
+                continue
+            Ln = longform.noise_len(T, W, O, Tp)
+            for x in mix.reshape(-1, T).to(device=dev, dtype=torch.float32).contiguous():
+                G = torch.empty((n_noise, 1, 1, Ln), dtype=torch.float32, device=dev)
+                for k in range(n_noise):   # the sampler's order: x0, then one z per intermediate step
+                    if rng is not None and rng.device != dev:
+                        G[k].copy_(torch.randn((1, 1, Ln), generator=rng, device=rng.device, dtype=torch.float32))
+                    else:
+                        torch.randn((1, 1, Ln), generator=rng, out=G[k])
+                xs.append(x)
+                Gs.append(G)
+                owner.append(i)
+        if xs:
+            B, slots = longform.pool([x.numel() for x in xs], W, O, batch)
+            N, C = len(slots), len(xs)
+            ys = [torch.empty_like(x) for x in xs]
+            clips = (L.PoolClip * C)()
+            for c in range(C):
+                clips[c] = L.PoolClip(xs[c].data_ptr(), Gs[c].data_ptr(), ys[c].data_ptr(), xs[c].numel(),
+                                      Gs[c].shape[-1])
+            lib = L.load()
+            fade = self._fade_table(O, dev)
+            fade_ptr = fade.data_ptr() if fade is not None else 0
+
+            def run():
+                # the plan, under the key in the plan LRU, of enhance() on a (B, W) batch
+                key, make_plan = self._plan_spec(B, W, n_steps, epsilon, keep_rms)
+                plan = self._arena_plan(key, 0, make_plan)
+                if plan.n_noise != n_noise or plan.Tp != Tp:
+                    raise L.OuHipError(f"enhance_long_many: the plan draws {plan.n_noise} x {plan.Tp}, expected "
+                                       f"{n_noise} x {Tp}")
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                sp = ctypes.c_void_p(stream)
+                for first in range(0, N, B):
+                    L.check(lib.ou_pool_gather(clips, C, W, O, first, B, n_noise, plan.Tp, plan.MIX.data_ptr(), W,
+                                               plan.NZ.data_ptr(), B * plan.Tp, plan.Tp, sp), "pool_gather")
+                    plan._launch(stream, True)
+                    L.check(lib.ou_pool_overlap_add(clips, C, W, O, first, B, plan.OUT.data_ptr(), W, fade_ptr, sp),
+                            "pool_overlap_add")
+                plan.check(pinned=True)   # once, after the last group
+
+            try:
+                run()
+            except L.OuRangeError as e:
+                # as enhance(): widen the named layers' exponents (or fall back
+                # to f32 operands) and rerun every pooled clip on the same
+                # noise; every sample of every result is stored again
+                self._range_recover(e, run)
+            for i, mix in enumerate(mixes):
+                rows = [y for y, o in zip(ys, owner) if o == i]
+                if rows:
+                    outs[i] = rows[0] if mix.ndim == 1 else torch.stack(rows) if mix.ndim == 2 \
+                        else torch.stack(rows)[:, None, :]
+        return outs
+
     def enhance_many(self, mixes, n_steps: Optional[int] = None, epsilon: Optional[float] = None,
                      rng: Optional[torch.Generator] = None, keep_rms: Optional[bool] = False, streams: int = 2,
                      pre_noise=None):

@@ -6,7 +6,12 @@ process.  Reports audio seconds / wall seconds for the whole run (model load,
 plan recording, tuning, file I/O included) and for the second pass over the
 same folder (warm process), and the device memory high-water mark of each.
 
-    python tools/cli_bench.py [--files 50] [--streams 2]
+Options this tool does not know are passed on to the CLI, so the windowed paths
+are measured on the same folder (that is ``enhance_long``'s result then, not
+``enhance()``'s):
+
+    python tools/cli_bench.py [--files 50] [--streams 2] [--out profiles/cli.json]
+    python tools/cli_bench.py --window 2 --overlap 0.25 [--window-pool]
 """
 import argparse
 import json
@@ -32,7 +37,8 @@ def main():
     ap.add_argument("--files", type=int, default=50)
     ap.add_argument("--streams", type=int, default=2)
     ap.add_argument("--profile", action="store_true", help="cProfile the second (warm) pass")
-    a = ap.parse_args()
+    ap.add_argument("--out", default=None, help="write the two result lines here as well")
+    a, cli_extra = ap.parse_known_args()
     from scipy.io import wavfile
 
     from open_universe_amd.bin import enhance as cli
@@ -59,7 +65,7 @@ def main():
     for rep in range(2):
         torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
-        argv = [noisy, os.path.join(tmp, f"out{rep}"), "--model", ckpt, "--streams", str(a.streams)]
+        argv = [noisy, os.path.join(tmp, f"out{rep}"), "--model", ckpt, "--streams", str(a.streams)] + cli_extra
         if a.profile and rep == 1:
             import cProfile
             import pstats
@@ -70,9 +76,12 @@ def main():
             cli.main(argv)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        rows.append({"pass": rep, "files": len(lengths), "audio_s": round(audio_s, 2), "wall_s": round(dt, 3),
-                     "xrt": round(audio_s / dt, 1), "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 2)})
+        rows.append({"pass": rep, "cli_options": " ".join(cli_extra), "files": len(lengths),
+                     "audio_s": round(audio_s, 2), "wall_s": round(dt, 3), "xrt": round(audio_s / dt, 1), "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 2)})
         print(json.dumps(rows[-1]), flush=True)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.writelines(json.dumps(r) + "\n" for r in rows)
 
 
 if __name__ == "__main__":

@@ -17,6 +17,13 @@ nothing about perceived quality: it only shows how far the two definitions are
 apart on this model.
 
     python tools/long_bench.py --out profiles/long_c64.json
+
+``--pool`` measures the pooled leg instead: two such clips (18 windows) through
+one ``enhance_long_many`` call, three replays of eight slots, against two
+consecutive ``enhance_long`` calls, four replays -- the same warm-up and timed
+call counts, one process, the same generator handed on from call to call.
+
+    python tools/long_bench.py --pool --out profiles/long_pool.json
 """
 import argparse
 import ctypes
@@ -90,10 +97,59 @@ def _kernel_ms(model, x, W, O, n_steps):
     return {k: statistics.median(v) for k, v in res.items()}, len(firsts)
 
 
+def pooled():
+    import numpy as np
+    import torch
+
+    import bench
+    from open_universe_amd import longform
+    from open_universe_amd.utils.synthetic import synth_audio
+
+    dev = torch.device("cuda:0")
+    cfg, model = bench.build_model(dev)
+    fs = int(cfg["fs"])
+    T, W, O = int(SECONDS * fs), int(WINDOW_S * fs), int(OVERLAP_S * fs)
+    xs = [torch.from_numpy(synth_audio(T, fs, i)[0].astype(np.float32)).to(dev) for i in range(2)]
+    sync = lambda: torch.cuda.synchronize(dev)   # noqa: E731
+    B, slots = longform.pool([T, T], W, O, BATCH)
+    out = {"shape": f"full-width PP16, synthetic weights, two {SECONDS:g} s clips at {fs} Hz, "
+                    f"{int(model.diff_kwargs.n_steps)} steps",
+           "window_s": WINDOW_S, "overlap_s": OVERLAP_S, "batch": BATCH, "warmup": WARMUP, "steps": STEPS,
+           "windows": len(slots)}
+    with torch.no_grad():
+        rng = torch.Generator(device=dev).manual_seed(1)
+        model.enhance(xs[0][:W], rng=rng)   # weights packed and tiles tuned outside both measurements
+        sync()
+        res = _timed(lambda: [model.enhance_long(x, W, O, batch=BATCH, rng=rng) for x in xs], sync)
+        res["replays"] = 2 * len(longform.groups(T, W, O, BATCH)[1])
+        out["enhance_long_twice"] = res
+        res = _timed(lambda: model.enhance_long_many(xs, W, O, batch=BATCH, rng=rng), sync)
+        res["replays"] = -(-len(slots) // B)
+        out["enhance_long_many"] = res
+        # the same seed: the same noise per clip, other neighbours in the groups
+        r7 = torch.Generator(device=dev).manual_seed(7)
+        seq = [model.enhance_long(x, W, O, batch=BATCH, rng=r7) for x in xs]
+        many = model.enhance_long_many(xs, W, O, batch=BATCH, rng=torch.Generator(device=dev).manual_seed(7))
+        out["rel_rms_many_vs_twice"] = [float(((a - b).double().square().mean() / b.double().square().mean()).sqrt())
+                                        for a, b in zip(many, seq)]
+    out["speedup"] = out["enhance_long_twice"]["median_ms"] / out["enhance_long_many"]["median_ms"]
+    out["range_fallbacks"], out["range_widenings"] = model.range_fallbacks, model.range_widenings
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=None, help="write the JSON here as well")
+    ap.add_argument("--pool", action="store_true", help="the pooled leg alone: enhance_long_many against two "
+                                                        "enhance_long calls")
     a = ap.parse_args()
+    if a.pool:
+        text = json.dumps(pooled(), indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
     import numpy as np
     import torch
 
