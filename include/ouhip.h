@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define OUHIP_ABI_VERSION 10
+#define OUHIP_ABI_VERSION 11
 
 int ou_abi_version(void);
 const char* ou_last_error(void);
@@ -464,6 +464,10 @@ int ou_snake_aa(const ou_snake_desc* d, void* stream);
  * Each conv applies its scalar PReLU slope to its input; frames outside
  * [0, length) are zero padding.  sc / film / cond_out / res2 are optional
  * (NULL).  y must not alias h, sc, cond_out or res2.
+ * Optional fourth stages on the block output, inside the same launch: the
+ * score head (head), the encoder's strided rate-change conv (w_down) and
+ * the decoder's up-sampling conv of the next level (w_up: y -> u, with the
+ * skip residual added in place and y itself not stored when NULL).
  * ---------------------------------------------------------------------- */
 typedef struct ou_block_desc {
     const float* h;            /* block input [B][C][T]                          */
@@ -543,6 +547,37 @@ typedef struct ou_block_desc {
     const uint16_t* xs;
     int64_t xs_bstride;        /* bytes between batch items                      */
     int32_t xs_rows, xs_pad_;  /* samples per 32-channel block (>= length)       */
+    /* 64 / 128 channels, prec 1 / 2 (ou_block_up_supported): the decoder's
+     * up-sampling PReLU_Conv that consumes the block output (blocks.py:221-225,
+     * 276-283) as a fourth stage, the FIR-applied form of ou_conv_desc.fir 2:
+     *   z[t up_rate + ph][co] = sum_ci w[ci][co][ph] PReLU_up(y)[t][ci]
+     *   v = FIR(z) (2 up_rate + 1 taps, 'same', z zero outside [0, up_rate *
+     *       length)) + b_up;   v = 0 at samples >= u_valid
+     *   u = (v + u_res) * s_u                      for samples < u_len
+     * A workgroup then owns ou_block_frames(C) - 2 frames (one halo frame of y
+     * on each side feeds the FIR).  up_taps NULL: no FIR (a plain transposed
+     * conv).  u_res NULL: no residual (s_u still applies); u_res may alias u
+     * exactly (the in-place skip add: each element is read and written by the
+     * same thread).  u must not alias h, sc, y or res2.  With w_up set, y may
+     * be NULL (the block output is not stored), the whole signal is computed
+     * (f0 = f1 = h0 = h1 = 0) and sy, head and w_down are not combined.  The
+     * PReLU_up(y) operand is staged with shift[3]; range code 16.           */
+    const void* w_up;          /* ou_block_pack_rect(up_rate * C / 2, C, 1) of the
+                                  rows 32 (co / P) + (co % P) up_rate + ph, P =
+                                  32 / up_rate (the fir 2 row order of
+                                  ou_conv_desc), or NULL: no up conv            */
+    const float* b_up;         /* [C / 2] or NULL                                */
+    const float* up_taps;      /* [2 up_rate + 1] or NULL                        */
+    float slope_up, w_up_unscale;
+    int32_t up_rate, up_pad_;
+    float* u;                  /* [B][C / 2][>= u_len]                           */
+    int64_t u_bstride, u_cstride;
+    int32_t u_len, u_valid;    /* samples stored (<= up_rate * length); zero-fill
+                                  from u_valid on                                */
+    const float* u_res;        /* skip residual or NULL                          */
+    int64_t ur_bstride, ur_cstride;
+    float s_u;
+    int32_t u_pad2_;
 } ou_block_desc;
 
 /* 1 when ou_block handles this channel count and operand precision. */
@@ -565,6 +600,8 @@ int64_t ou_block_packed_f32(int channels, int kt);
 int ou_block_pack_f32(const float* w, int channels, int kt, float* out, float* w_unscale);
 /* 1 when ou_block fuses the rate-change conv for (channels, rate, kt, prec). */
 int ou_block_down_supported(int channels, int rate, int kt, int prec);
+/* 1 when ou_block fuses the up-sampling conv for (channels, rate, prec). */
+int ou_block_up_supported(int channels, int rate, int prec);
 int ou_block(const ou_block_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------

@@ -12,7 +12,7 @@ from ctypes import POINTER, c_char, c_char_p, c_float, c_int, c_int32, c_int64, 
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OUHIP_LIB", os.path.join(_HERE, "libouhip.so"))
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 fp = c_void_p  # device pointers are passed as integers
 
@@ -150,6 +150,10 @@ class BlockDesc(ctypes.Structure):
         ("sy", fp), ("sy_bstride", c_int64), ("sy_rows", c_int32), ("sy_shift", c_int32),
         ("sy_slope", c_float), ("sy_pad_", c_int32),
         ("xs", fp), ("xs_bstride", c_int64), ("xs_rows", c_int32), ("xs_pad_", c_int32),
+        ("w_up", fp), ("b_up", fp), ("up_taps", fp), ("slope_up", c_float), ("w_up_unscale", c_float),
+        ("up_rate", c_int32), ("up_pad_", c_int32),
+        ("u", fp), ("u_bstride", c_int64), ("u_cstride", c_int64), ("u_len", c_int32), ("u_valid", c_int32),
+        ("u_res", fp), ("ur_bstride", c_int64), ("ur_cstride", c_int64), ("s_u", c_float), ("u_pad2_", c_int32),
     ]
 
 
@@ -216,6 +220,7 @@ EXPORTS = {
     "ou_block_pack_f32": (c_int, [POINTER(c_float), c_int, c_int, POINTER(c_float), POINTER(c_float)]),
     "ou_block_pack_rect": (c_int, [POINTER(c_float), c_int, c_int, c_int, c_void_p, POINTER(c_float)]),
     "ou_block_down_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "ou_block_up_supported": (c_int, [c_int, c_int, c_int]),
     "ou_block": (c_int, [POINTER(BlockDesc), c_void_p]),
     "ou_resample": (c_int, [fp, c_int64, fp, c_int64, c_int, c_int, c_int, fp, c_int, c_int, c_int, c_int,
                             c_void_p]),

@@ -19,7 +19,10 @@
 // residual re-read) of a C x T tensor to 1 read + 1 write, and 3 kernel
 // latencies become 1.  Halo frames are recomputed by the neighbouring
 // workgroup (F = 124 / 60 / 28 frames at C = 32 / 64 / 128; 124 / 60 at
-// PP24's 96 / 192).
+// PP24's 96 / 192).  Whatever consumes y alone can run as a fourth stage of
+// the same launch (kEpiHead, kEpiDown, kEpiUp below): the score head, the
+// encoder's strided rate-change conv, the next decoder level's up-sampling
+// conv -- with the last, y is not written to HBM at all.
 //
 // Arithmetic is the split-f16 form of ou_conv (P = 1): every operand is
 // v = hi + lo * 2^-11 (f16 halves; weights packed by ou_block_pack with a
@@ -322,12 +325,22 @@ constexpr int kEpiIn = 16, kEpiHead = 32;
 // covers the conv's sample halo (R (KF-1)/2 on each side) and a workgroup owns
 // a multiple of R frames.
 constexpr int kEpiDown = 64;
+// kEpiUp: the decoder's up-sampling conv that consumes the block output
+// (blocks.py:221-225,276-283) as a fourth stage, in the FIR-applied form of
+// conv_fukernel (ou_conv.hip): the transposed conv is a one-tap K = C GEMM on
+// PReLU_up(y) with R C / 2 rows (32 / R whole channels per m-tile), its
+// results go to an f32 sample image in LDS, the (2R+1)-tap FIR runs over that
+// image on the VALU, then bias, the valid_len zero-fill, the skip residual and
+// the store.  conv3 covers one extra frame on each side (the FIR reaches R
+// samples), so a workgroup owns F - 2 frames; y itself is stored only when the
+// descriptor names a buffer.
+constexpr int kEpiUp = 128;
 
 // conv3 frames before t0 (the halo of whatever consumes the block output)
 template <int EPI, int R, int KF>
 constexpr int block_off()
 {
-    return (EPI & kEpiHead) ? 1 : (EPI & kEpiDown) ? R * ((KF - 1) / 2) : 0;
+    return (EPI & (kEpiHead | kEpiUp)) ? 1 : (EPI & kEpiDown) ? R * ((KF - 1) / 2) : 0;
 }
 
 template <int C, int NT, int P, int EPI, int R = 1, int KF = 1>
@@ -337,7 +350,29 @@ constexpr int block_f()
         constexpr int halo = 2 * R * ((KF - 1) / 2);
         return (BCfg<C, NT, P>::NF - 4 - halo) / R * R;
     }
-    return BCfg<C, NT, P>::NF - 4 - ((EPI & kEpiHead) ? 2 : 0);
+    return BCfg<C, NT, P>::NF - 4 - ((EPI & (kEpiHead | kEpiUp)) ? 2 : 0);
+}
+
+// kEpiUp's f32 sample image Y [C / 2 channels][(F + 2) R samples + 4] (the
+// frames whose conv3 result is complete; F = 32 NT - 6) lies over region B
+// (free once conv2 has read it) and past it: the dynamic LDS of these
+// instantiations grows to hold it (C = 128, split-f16: 49 KB instead of
+// 38 KB -- three workgroups per CU, as the plain block runs)
+template <int C, int NT, int R>
+constexpr int up_yrs()
+{
+    return (32 * NT - 4) * R + 4;
+}
+
+template <int C, int NT, int P, int EPI, int R>
+constexpr int block_lds()
+{
+    using K = BCfg<C, NT, P>;
+    if constexpr (EPI & kEpiUp) {
+        constexpr int up = (int)sizeof(typename K::E) * K::B_OFF + (C / 2) * up_yrs<C, NT, R>() * 4;
+        return up > K::LDS_BYTES ? up : K::LDS_BYTES;
+    }
+    return K::LDS_BYTES;
 }
 
 typedef float float2_t __attribute__((ext_vector_type(2)));
@@ -421,6 +456,148 @@ __device__ __forceinline__ void down_stage(const ou_block_desc& d, const _Float1
     }
 }
 
+constexpr int kBlkSentinel = 0x7ffffff0;   // byte offset past any buffer: loads return 0
+
+// kEpiUp's fourth stage on region A (rows w <-> frames t0 - 1 + w, PReLU_up(y)
+// split like every stage input, zero outside [0, T) and past row F + 1).
+// GEMM: R C / 2 rows x 32 NT frames, K = C; packed row 32 (co / CPT) +
+// (co % CPT) R + ph (CPT = 32 / R whole channels per m-tile), dealt as 32 x 32
+// tiles over the 4 waves; results -> Y[co][w R + ph], i.e. sample
+// (t0 - 1) R + index.  Then thread items of (channel, 4 consecutive samples):
+// output sample t0 R + sig reads Y[sig .. sig + 2R] (the FIR, centred on index
+// sig + R), adds the bias, zero-fills from u_valid, adds the residual and
+// stores -- conv_fukernel's epilogue without FiLM and res2.
+template <int C, int NT, int P, int R, int F, int SX>
+__device__ __forceinline__ void up_stage(const ou_block_desc& d, const _Float16* xa, int pstride, float* Y, int t0,
+                                         int TS, int b, int wave, int lane, int tid)
+{
+    constexpr int KS = C / 16, CO = C / 2, CPT = 32 / R, M4 = CO / CPT, N4 = NT;
+    constexpr int YRS = up_yrs<C, NT, R>();
+    constexpr int D = KS < 6 ? KS : 6;
+    static_assert(32 % R == 0 && CO % CPT == 0, "up stage: whole channels per m-tile");
+    const int l32 = lane & 31, h = lane >> 5;
+    const half8_t* wp = (const half8_t*)d.w_up;
+    const float un = d.w_up_unscale * ou_exp2i(d.shift[3] - kStageShift);
+
+    // ---- the epilogue's items: (channel co, 4 consecutive samples)
+    constexpr int NTAP = 2 * R + 1;
+    constexpr int NW = (4 + 2 * R + 3) / 4 * 4;   // window floats read (16-B reads)
+    constexpr int NSG = (F * R + 3) / 4;          // 4-sample groups per channel
+    constexpr int NIT = CO * NSG;                 // items of the workgroup
+    constexpr int UEI = (NIT + 255) / 256;
+    static_assert(4 * (NSG - 1) + NW <= YRS && YRS % 4 == 0 && (F + 2) * R <= YRS,
+                  "up stage: FIR window inside the sample image");
+    const bool fir = d.up_taps != nullptr, has_r = d.u_res != nullptr;
+    const int vlen = d.u_valid;
+    const int tend = min(min(t0 + F, TS) * R, d.u_len);   // samples [t0 R, tend) are stored
+    const int ucs = (int)d.u_cstride, rcs = (int)d.ur_cstride;
+    const __amdgpu_buffer_rsrc_t us = ou_rsrc(d.u + (int64_t)b * d.u_bstride, (int64_t)CO * ucs * 4);
+    const __amdgpu_buffer_rsrc_t rs =
+        ou_rsrc(has_r ? d.u_res + (int64_t)b * d.ur_bstride : d.u, has_r ? (int64_t)CO * rcs * 4 : 0);
+    // 16-B residual loads and stores where the window's first sample and every
+    // row start are 16-B aligned (uniform over the workgroup)
+    const bool v4 = ((t0 * R) & 3) == 0 && ((uintptr_t)d.u % 16) == 0 && d.u_bstride % 4 == 0 && ucs % 4 == 0 &&
+                    (!has_r || (((uintptr_t)d.u_res % 16) == 0 && d.ur_bstride % 4 == 0 && rcs % 4 == 0));
+
+    for (int tile = wave; tile < M4 * N4; tile += 4) {
+        const int m4 = tile % M4, n4 = tile / M4;
+        const int w = n4 * 32 + l32;
+        const _Float16* xb = xa + w * SX + 8 * h;
+        floatx16 acc, accx;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f, accx[r] = 0.f;
+        half8_t ra[D][2];
+        auto load_a = [&](int s, half8_t (&dst)[2]) {
+            const half8_t* p = wp + (((int64_t)m4 * KS + s) * 2) * 64 + lane;
+            dst[0] = p[0];
+            if constexpr (P == 1) dst[1] = p[64];
+        };
+#pragma unroll
+        for (int s = 0; s < D - 1; ++s) load_a(s, ra[s]);
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            if (s + D - 1 < KS) load_a(s + D - 1, ra[(s + D - 1) % D]);
+            const _Float16* q = xb + 16 * s;
+            const half8_t bq = *(const half8_t*)q;
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ra[s % D][0], bq, acc, 0, 0, 0);
+            if constexpr (P == 1) {
+                const half8_t bl = *(const half8_t*)(q + pstride);
+                accx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ra[s % D][0], bl, accx, 0, 0, 0);
+                accx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ra[s % D][1], bq, accx, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int ml = (r & 3) + 8 * (r >> 2) + 4 * h;   // row within the m-tile
+            const int cl = ml / R, ph = ml - (ml / R) * R;
+            if (w < F + 2) Y[(m4 * CPT + cl) * YRS + w * R + ph] = __builtin_fmaf(accx[r], 1.f / 2048.f, acc[r]) * un;
+        }
+    }
+    // every item's skip residual is requested here, ahead of the barrier: inside
+    // the item loop each load would wait for the previous item's store (u_res
+    // may alias u), and before the GEMM they cost spills at C = 128.  An item
+    // reads and writes only its own samples.
+    float rv[UEI][4];
+#pragma unroll
+    for (int e = 0; e < UEI; ++e) {
+        const int it = min(tid + 256 * e, NIT - 1);
+        const int co = it / NSG, sig = 4 * (it - (it / NSG) * NSG);
+        const int s0 = t0 * R + sig;
+        if (v4 && sig + 3 < F * R && s0 + 3 < tend) {
+            const ou_u4_t a1 = __builtin_amdgcn_raw_buffer_load_b128(rs, (co * rcs + s0) * 4, 0, 0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) rv[e][k] = __uint_as_float(a1[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                rv[e][k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                    rs, (sig + k < F * R && s0 + k < tend) ? (co * rcs + s0 + k) * 4 : kBlkSentinel, 0, 0));
+        }
+    }
+    __syncthreads();
+
+    float tap[NTAP];
+#pragma unroll
+    for (int j = 0; j < NTAP; ++j) tap[j] = fir ? d.up_taps[j] : 0.f;
+#pragma unroll
+    for (int e = 0; e < UEI; ++e) {
+        const int it = tid + 256 * e;
+        if (NIT % 256 != 0 && it >= NIT) break;
+        const int co = it / NSG, sig = 4 * (it - (it / NSG) * NSG);
+        const int s0 = t0 * R + sig;
+        float win[NW];
+        const float* yr = Y + co * YRS + sig;
+#pragma unroll
+        for (int k = 0; k < NW; k += 4) {
+            const f32x4_t q4 = *(const f32x4_t*)(yr + k);
+            win[k] = q4[0], win[k + 1] = q4[1], win[k + 2] = q4[2], win[k + 3] = q4[3];
+        }
+        const float bias = d.b_up ? d.b_up[co] : 0.f;
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float f = 0.f;
+#pragma unroll
+            for (int j = 0; j < NTAP; ++j) f = __builtin_fmaf(tap[j], win[k + j], f);
+            if (!fir) f = win[k + R];
+            o[k] = s0 + k >= vlen ? 0.f : f + bias;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = (o[k] + rv[e][k]) * d.s_u;
+        if (v4 && sig + 3 < F * R && s0 + 3 < tend) {   // a whole aligned group: one 16-B store
+            __builtin_amdgcn_raw_buffer_store_b128(
+                ou_u4_t{__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])}, us,
+                (co * ucs + s0) * 4, 0, 0);
+            continue;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            __builtin_amdgcn_raw_buffer_store_b32(
+                __float_as_uint(o[k]), us,
+                (sig + k < F * R && s0 + k < tend) ? (co * ucs + s0 + k) * 4 : kBlkSentinel, 0, 0);
+    }
+}
+
 template <int C>
 constexpr int block_threads()
 {
@@ -430,17 +607,18 @@ constexpr int block_threads()
 // resident workgroups per CU the register budget is sized for: two (256
 // VGPRs a lane) where a wave owns one or two M tiles; one (512) for PP24's
 // 96 / 192 channels, whose waves own three M tiles (their ~107 KB of LDS
-// allows one workgroup per CU anyway)
-template <int C>
+// allows one workgroup per CU anyway).  The kEpiUp variants are held to three
+// (168 VGPRs; their LDS, 49 KB at most, allows it): the plain 64- and 128-
+// channel blocks happen to fit three, and with two the fused stage loses more
+// to the lost residency than it saves (1105 / 617 workgroups on 256 CUs).
+template <int C, int EPI = 0>
 constexpr int block_min_wgs()
 {
-    return (C == 96 || C == 192) ? 1 : 2;
+    return (C == 96 || C == 192) ? 1 : (EPI & kEpiUp) ? 3 : 2;
 }
 
-constexpr int kBlkSentinel = 0x7ffffff0;   // byte offset past any buffer: loads return 0
-
 template <int C, int NT, int P, int EPI, int R = 1, int KF = 1>
-__global__ __launch_bounds__(block_threads<C>(), block_min_wgs<C>()) void block_kernel(ou_block_desc d)
+__global__ __launch_bounds__(block_threads<C>(), (block_min_wgs<C, EPI>())) void block_kernel(ou_block_desc d)
 {
     using K = BCfg<C, NT, P>;
     ou_kernarg_prefetch8();
@@ -861,12 +1039,16 @@ __global__ __launch_bounds__(block_threads<C>(), block_min_wgs<C>()) void block_
                 ou_rsrc(d.sy ? (const char*)d.sy + (int64_t)b * d.sy_bstride : (const char*)yb,
                         d.sy ? (int64_t)(C / 32) * d.sy_rows * 128 : 0);
             const float sscale = ou_exp2i(-d.sy_shift);
-            const __amdgpu_buffer_rsrc_t yrs = ou_rsrc(yb, (int64_t)C * d.y_cstride * 4);
+            // kEpiUp without a y buffer: an empty resource drops every store
+            const __amdgpu_buffer_rsrc_t yrs =
+                ou_rsrc(yb, ((EPI & kEpiUp) && !d.y) ? 0 : (int64_t)C * d.y_cstride * 4);
             // kEpiDown: PReLU_down(y) 2^-6 also goes to region A (split), rows
             // w <-> frames t0 - OFF + w, zero outside [0, T) and past the rows
             // the strided conv reads
-            if constexpr (EPI & kEpiDown) __syncthreads();   // every wave is done reading region A
-            const float ad = (EPI & kEpiDown) ? d.slope_down : 0.f;
+            // kEpiUp: PReLU_up(y) likewise, rows w < F + 2 (the frames whose
+            // conv3 result is complete)
+            if constexpr (EPI & (kEpiDown | kEpiUp)) __syncthreads();   // every wave is done reading region A
+            const float ad = (EPI & kEpiDown) ? d.slope_down : (EPI & kEpiUp) ? d.slope_up : 0.f;
 #pragma unroll
             for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
@@ -904,8 +1086,8 @@ __global__ __launch_bounds__(block_threads<C>(), block_min_wgs<C>()) void block_
                                             sscale, d.sy_slope, oms);
                         }
                     }
-                    if constexpr (EPI & kEpiDown) {
-                        constexpr int RH = R * (KF - 1 - (KF - 1) / 2);
+                    if constexpr (EPI & (kEpiDown | kEpiUp)) {
+                        constexpr int RH = (EPI & kEpiUp) ? 1 : R * (KF - 1 - (KF - 1) / 2);
                         const float keep = (t >= 0 && t < T && w < F + OFF + RH) ? kInD : 0.f;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
@@ -928,6 +1110,10 @@ __global__ __launch_bounds__(block_threads<C>(), block_min_wgs<C>()) void block_
                 __syncthreads();
                 down_stage<C, P, R, KF, F, SX>(d, xa, K::PA, t0, T, TS, b, wave, lane);
             }
+            if constexpr (EPI & kEpiUp) {
+                __syncthreads();
+                up_stage<C, NT, P, R, F, SX>(d, xa, K::PA, (float*)xbuf, t0, TS, b, wave, lane, tid);
+            }
         }
     }
     // range codes: 1 / 2 / 8 / 16 the conv1 / conv2 / conv3 / down input's
@@ -937,7 +1123,7 @@ __global__ __launch_bounds__(block_threads<C>(), block_min_wgs<C>()) void block_
         ou_range_flag(d.status, om0, 1, lane);
         ou_range_flag(d.status, om1, 2, lane);
         ou_range_flag(d.status, om2, 8, lane);
-        if constexpr ((EPI & kEpiDown) != 0) ou_range_flag(d.status, omd, 16, lane);
+        if constexpr ((EPI & (kEpiDown | kEpiUp)) != 0) ou_range_flag(d.status, omd, 16, lane);
         if (d.sy) ou_range_flag(d.status, oms, 32, lane);
     }
 }
@@ -946,20 +1132,21 @@ template <int C, int NT, int P, int EPI, int R = 1, int KF = 1>
 int launch(const ou_block_desc& d, hipStream_t s)
 {
     using K = BCfg<C, NT, P>;
+    constexpr int LDS = block_lds<C, NT, P, EPI, R>();
     static bool attr = false;
     if (!attr) {
         OU_HIP_CHECK(hipFuncSetAttribute((const void*)block_kernel<C, NT, P, EPI, R, KF>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS),
                      "block: LDS attribute");
         attr = true;
     }
     constexpr int F = block_f<C, NT, P, EPI, R, KF>();
-    static_assert(F > 0 && F % R == 0, "block: frames per workgroup");
+    static_assert(F > 0 && (F % R == 0 || (EPI & kEpiUp)), "block: frames per workgroup");
     const int f1 = d.f1 > 0 ? min(d.f1, d.length) : d.length;
     if (d.f0 < 0 || d.f0 >= f1 || d.f0 % R || (R > 1 && f1 % R && f1 != d.length))
         return ou_fail(-1, "block: frame range [%d, %d) (rate %d, length %d)", d.f0, f1, R, d.length);
     dim3 grid((f1 - d.f0 + F - 1) / F, d.batch);
-    hipLaunchKernelGGL((block_kernel<C, NT, P, EPI, R, KF>), grid, dim3(K::NTH), K::LDS_BYTES, s, d);
+    hipLaunchKernelGGL((block_kernel<C, NT, P, EPI, R, KF>), grid, dim3(K::NTH), LDS, s, d);
     return ou_check_launch("block");
 }
 
@@ -987,12 +1174,38 @@ int launch_down(const ou_block_desc& d, hipStream_t s)
     return ou_fail(-1, "block: no fused rate-change conv for %d channels, rate %d, kt %d", C, d.rate, d.down_kt);
 }
 
+// up-sampling variants instantiated: the score decoder's 128 -> 64 channel
+// rate-4 and 64 -> 32 channel rate-2 convs (PP16 / ORIG16), after the fused
+// 128- and 64-channel blocks
+constexpr bool up_ok(int C, int rate)
+{
+    return (C == 128 && rate == 4) || (C == 64 && rate == 2);
+}
+
+template <int C, int NT, int P, int EPI>
+int launch_up(const ou_block_desc& d, hipStream_t s)
+{
+    if constexpr (C == 128) {
+        if (d.up_rate == 4) return launch<C, NT, P, EPI, 4>(d, s);
+    } else if constexpr (C == 64) {
+        if (d.up_rate == 2) return launch<C, NT, P, EPI, 2>(d, s);
+    }
+    return ou_fail(-1, "block: no fused up-sampling conv for %d channels, rate %d", C, d.up_rate);
+}
+
 template <int C, int NT, int P>
 int launch_epi(const ou_block_desc& d, hipStream_t s)
 {
     const int epi = (d.film ? kEpiFilm : 0) | (d.sc ? kEpiSc : 0) | (d.cond_out ? kEpiCond : 0) |
                     (d.res2 ? kEpiRes2 : 0) | (d.x ? kEpiIn : 0) | (d.head.w ? kEpiHead : 0) |
-                    (d.w_down ? kEpiDown : 0);
+                    (d.w_down ? kEpiDown : 0) | (d.w_up ? kEpiUp : 0);
+    if constexpr ((C == 64 || C == 128) && P != 0) {   // decoder blocks with the next level's up conv
+        switch (epi) {
+        case kEpiUp: return launch_up<C, NT, P, kEpiUp>(d, s);
+        case kEpiFilm | kEpiUp: return launch_up<C, NT, P, kEpiFilm | kEpiUp>(d, s);
+        case kEpiFilm | kEpiSc | kEpiUp: return launch_up<C, NT, P, kEpiFilm | kEpiSc | kEpiUp>(d, s);
+        }
+    }
     if constexpr ((C == 32 || C == 64) && P != 0) {   // encoder blocks with their rate-change conv
         switch (epi) {
         case kEpiDown: return launch_down<C, NT, P, kEpiDown>(d, s);
@@ -1060,6 +1273,13 @@ extern "C" int ou_block_supported(int channels, int prec)
 extern "C" int ou_block_down_supported(int channels, int rate, int kt, int prec)
 {
     return prec != 0 && ou_block_supported(channels, prec) && down_ok(channels, rate, kt);
+}
+
+// Measured per level at PP16 8 s shapes (tools/block_bench.py --up, DESIGN.md
+// section 3): a level that does not beat block + conv_fukernel leaves up_ok.
+extern "C" int ou_block_up_supported(int channels, int rate, int prec)
+{
+    return (prec == 1 || prec == 2) && ou_block_supported(channels, prec) && up_ok(channels, rate);
 }
 
 extern "C" int ou_block_frames(int channels)
@@ -1157,8 +1377,24 @@ extern "C" int ou_block(const ou_block_desc* dp, void* stream)
 {
     if (!dp) return ou_fail(-1, "block: null descriptor");
     const ou_block_desc& d = *dp;
-    if (!d.h || !d.y || !d.w[0] || !d.w[1] || !d.w[2] || d.length <= 0 || d.batch <= 0 || d.batch > 65535)
+    if (!d.h || (!d.y && !d.w_up) || !d.w[0] || !d.w[1] || !d.w[2] || d.length <= 0 || d.batch <= 0 ||
+        d.batch > 65535)
         return ou_fail(-1, "block: invalid descriptor");
+    if (d.w_up) {
+        const int co = d.channels / 2;
+        if (!ou_block_up_supported(d.channels, d.up_rate, d.prec))
+            return ou_fail(-1, "block: no fused up-sampling conv for %d channels, rate %d, prec %d", d.channels,
+                           d.up_rate, d.prec);
+        if (!d.u || d.sy || d.head.w || d.w_down || d.f0 || d.f1 || d.h0 || d.h1 || d.u_len <= 0 ||
+            d.u_len > (int64_t)d.up_rate * d.length || d.u_cstride < d.u_len || (d.u_res && d.ur_cstride < d.u_len) ||
+            !(d.w_up_unscale > 0.f) || (int64_t)co * d.u_cstride * 4 >= kBlkSentinel ||
+            (d.u_res && (int64_t)co * d.ur_cstride * 4 >= kBlkSentinel))
+            return ou_fail(-1, "block: the up-sampling stage needs u, the whole signal, 0 < u_len <= rate * length "
+                               "<= row strides, and no sy / head / w_down");
+        const void* no[4] = {d.h, d.sc, d.y, d.res2};
+        for (const void* p : no)
+            if (p && p == (const void*)d.u) return ou_fail(-1, "block: u aliases h, sc, y or res2");
+    }
     if (!ou_block_supported(d.channels, d.prec))
         return ou_fail(-1, "block: channels %d / prec %d not supported", d.channels, d.prec);
     // buffer resources take 32-bit offsets with a sentinel for "outside":

@@ -157,7 +157,7 @@ def _split_producer(op, p):
         if p.prec != 1 or p.rout != 1 or p.m % 32 or p.sy or p.f0:
             return None
         return (p.y, p.y_bstride, p.y_cstride, p.out_len, p.m, p.batch)
-    if (p.prec != 1 or p.head.w or p.sy or p.channels % 32 or p.f0 or p.f1):
+    if (p.prec != 1 or p.head.w or p.sy or p.channels % 32 or p.f0 or p.f1 or p.w_up):
         return None
     return (p.y, p.y_bstride, p.y_cstride, p.length, p.channels, p.batch)
 
@@ -568,6 +568,22 @@ class BlockW:
     rate_conv: Optional[ConvW] = None
     fused: Optional[FusedW] = None
     down: Optional[DownW] = None
+    up: Optional["UpW"] = None   # an up block's rate_conv packed for the preceding block's fused stage
+
+
+@dataclass
+class UpW:
+    """A decoder block's up-sampling conv packed for the fourth stage of the
+    block that produces its input (ou_block_desc.w_up): rows 32 (co // P) +
+    (co % P) rate + ph over ``cin`` input channels, one tap; ``taps`` is the
+    binomial FIR on the device, or None for a plain transposed conv."""
+    w: torch.Tensor
+    unscale: float
+    bias: Optional[torch.Tensor]
+    slope: float
+    rate: int
+    cin: int
+    taps: Optional[torch.Tensor]
 
 
 def fuse_blocks_enabled():
@@ -632,18 +648,51 @@ def prep_down_fused(spec, C, prec, bias, device):
     return DownW(torch.from_numpy(packed).to(device), un, bias, float(spec.slope), r, kt)
 
 
+def fuse_up_enabled():
+    """OUHIP_FUSE_UP=0 keeps the decoder's up-sampling convs as their own launches."""
+    import os
+
+    return os.environ.get("OUHIP_FUSE_UP", "1") != "0"
+
+
+def prep_up_fused(spec, prec, bias, device):
+    """An up-sampling conv (spec_up) in ou_block's layout (UpW) for the block
+    that produces its input, or None where ou_block has no such stage."""
+    r, cin = spec.rout, spec.cin
+    cout = spec.w.shape[0] // r
+    if not (fuse_up_enabled() and fuse_blocks_enabled() and spec.cm and spec.frame == 1 and 2 * cout == cin
+            and 32 % r == 0 and cout % (32 // r) == 0 and L.load().ou_block_up_supported(cin, r, prec)):
+        return None
+    if spec.fir is not None and spec.fir[0] == 2:   # anti-aliased: the unfolded rows and the FIR taps
+        wu, taps = np.asarray(spec.fir[2]), np.ascontiguousarray(spec.fir[3], np.float32)
+    elif spec.w.shape[2] == 1:                      # plain transposed conv: rows co * r + ph -> the same order
+        P = 32 // r
+        m = np.arange(r * cout)
+        co, ph = m // r, m % r
+        wu = np.zeros((r * cout, cin), np.float64)
+        wu[32 * (co // P) + (co % P) * r + ph] = spec.w[:, :, 0]
+        taps = None
+    else:
+        return None
+    packed, un = L.block_pack_np(np.ascontiguousarray(wu, np.float32)[:, :, None])
+    return UpW(torch.from_numpy(packed).to(device), un, bias, float(spec.slope), r, cin,
+               None if taps is None else torch.from_numpy(taps).to(device))
+
+
 def prep_block(sd, p, kind, rate, antialias, device):
     specs = [spec_same(sd, p + ".conv1", 5), spec_same(sd, p + ".conv2", 3), spec_same(sd, p + ".conv3", 3)]
     c1, c2, c3 = (make_conv(sp, device) for sp in specs)
-    rc, rc_spec = None, None
+    rc, rc_spec, up = None, None, None
     if kind == "down":
         rc_spec = spec_down(sd, p + ".rate_change_conv", rate, antialias)
         rc = make_conv(rc_spec, device)
     elif kind == "up":
-        rc = prep_up(sd, p + ".rate_change_conv", rate, antialias, device)
+        up_spec = spec_up(sd, p + ".rate_change_conv", rate, antialias)
+        rc = make_conv(up_spec, device)
+        up = prep_up_fused(up_spec, rc.prec, rc.bias, device) if rc.prec in (1, 2) else None
     fused = prep_fused(specs, c1.m, c1.prec, device) if c1.prec in (1, 2) else None
     down = prep_down_fused(rc_spec, c1.m, c1.prec, rc.bias, device) if (fused and rc_spec) else None
-    return BlockW(c1.m, kind, rate, c1, c2, c3, rc, fused, down)
+    return BlockW(c1.m, kind, rate, c1, c2, c3, rc, fused, down, up)
 
 
 @dataclass
@@ -784,7 +833,7 @@ def conv_desc(cw: ConvW, x: Act, y: Act, *, in_len=None, n_frames=None, out_len=
 
 def rec_block(prog, bw: BlockW, h: Act, out: Act, tA: Act, tB: Act, film=0, film_bs=0,
               sc: Act = None, res2: Act = None, s2=1.0, cond_out: Act = None, skip_tail=False,
-              x_in=None, head=None, e_out: Act = None, after_c1=None):
+              x_in=None, head=None, e_out: Act = None, after_c1=None, up=None, store_out=True):
     """ConvBlock main stage (blocks.py:393-407):
        cond_out = conv1(h); c = (cond_out + sc)/sqrt2; c = film(c); c = conv3(conv2(c));
        out = (h + c)/sqrt2 [; out = (out + res2) * s2]
@@ -792,7 +841,11 @@ def rec_block(prog, bw: BlockW, h: Act, out: Act, tA: Act, tB: Act, film=0, film
     rate_conv(out) (blocks.py:268-275): fused into the block where ou_block
     has the stage, else its own launch.  after_c1(): recorded as soon as
     conv1 (cond_out) is done -- right after conv1's launch in the unfused
-    form, after the block in the fused one."""
+    form, after the block in the fused one.  ``up`` = (UpW, d_up): the next
+    decoder level's up-sampling conv, given as its ou_conv descriptor d_up
+    (input ``out``), runs as the fused block's fourth stage; with
+    ``store_out`` False nothing else reads ``out`` and it is not stored.
+    Returns True when ``up`` was fused (else the caller records d_up)."""
     c1_out = cond_out if cond_out is not None else tA
     d1 = conv_desc(bw.conv1, h, c1_out, res1=sc, s1=NF2, film=film, film_bs=film_bs)
     if skip_tail:
@@ -806,16 +859,21 @@ def rec_block(prog, bw: BlockW, h: Act, out: Act, tA: Act, tB: Act, film=0, film
     if bw.fused is not None and out.ptr != h.ptr:
         fuse_rc = d_rc is not None and bw.down is not None
         descs = (d1, d2, d3) + ((x_in[4],) if x_in is not None else ()) + ((d_rc,) if fuse_rc else ())
+        fuse_up = (up is not None and up[0] is not None and up[0].cin == bw.C and head is None and not fuse_rc
+                   and fuse_up_enabled())
+        if fuse_up:
+            descs = descs + (up[1],)
         bd = block_desc(bw, h, out, descs, sc=sc, film=film, film_bs=film_bs,
                         cond_out=cond_out, res2=res2, s2=s2,
                         x_in=x_in[:4] if x_in is not None else None, head=head,
-                        e_out=e_out if fuse_rc else None)
+                        e_out=e_out if fuse_rc else None, up=up if fuse_up else None,
+                        store_out=store_out or not fuse_up)
         prog.add(L.OP_BLOCK, bd)
         if after_c1 is not None:
             after_c1()
         if d_rc is not None and not fuse_rc:
             add_conv(prog, d_rc)
-        return
+        return fuse_up
     assert x_in is None and head is None, "input / head fusion needs the fused block"
     add_conv(prog, d1)
     if after_c1 is not None:
@@ -824,6 +882,7 @@ def rec_block(prog, bw: BlockW, h: Act, out: Act, tA: Act, tB: Act, film=0, film
     add_conv(prog, d3)
     if d_rc is not None:
         add_conv(prog, d_rc)
+    return False
 
 
 def fir_desc(d):
@@ -870,13 +929,15 @@ def add_conv(prog, d):
 
 
 def block_desc(bw: BlockW, h: Act, out: Act, descs, sc: Act = None, film=0, film_bs=0, cond_out: Act = None,
-               res2: Act = None, s2=1.0, x_in=None, head=None, e_out: Act = None):
+               res2: Act = None, s2=1.0, x_in=None, head=None, e_out: Act = None, up=None, store_out=True):
     """ou_block descriptor of a ConvBlock's main path; ``descs`` are the
     equivalent ou_conv descriptors (their shape checks have run; their
     algorithmic FLOPs and bytes -- the unfused reference ops -- are kept).
     x_in = (x Act, in_scale ptr, w_in, b_in): compute h from the score input
     conv instead of reading it; head: an ou_head descriptor run on the block
-    output instead of storing it."""
+    output instead of storing it; up = (UpW, the up conv's ou_conv descriptor):
+    the fourth stage kEpiUp, with the block output itself stored only if
+    ``store_out``."""
     fw = bw.fused
     d = L.BlockDesc()
     d.h, d.h_bstride, d.h_cstride = h.ptr, h.bs, h.cs
@@ -919,6 +980,24 @@ def block_desc(bw: BlockW, h: Act, out: Act, descs, sc: Act = None, film=0, film
         d.b_down = dn.bias.data_ptr() if dn.bias is not None else 0
         d.slope_down, d.rate, d.down_kt = dn.slope, dn.rate, dn.kt
         d.e, d.e_bstride, d.e_cstride = e_out.ptr, e_out.bs, e_out.cs
+    if up is not None:
+        uw, du = up
+        assert uw.cin == bw.C and du.x == out.ptr and du.in_len == h.T and du.n_frames == h.T and du.batch == h.B
+        assert du.m == uw.rate * (bw.C // 2) and 0 < du.out_len <= uw.rate * h.T and not du.res2 and not du.film
+        assert du.y not in (h.ptr, out.ptr) and du.y_cstride >= du.out_len
+        d.w_up, d.w_up_unscale = uw.w.data_ptr(), uw.unscale
+        d.b_up = uw.bias.data_ptr() if uw.bias is not None else 0
+        d.up_taps = uw.taps.data_ptr() if uw.taps is not None else 0
+        d.slope_up, d.up_rate = uw.slope, uw.rate
+        d.u, d.u_bstride, d.u_cstride = du.y, du.y_bstride, du.y_cstride
+        d.u_len, d.u_valid = du.out_len, min(du.valid_len, 1 << 30)
+        if du.res1:
+            assert du.r1_cstride >= du.out_len
+            d.u_res, d.ur_bstride, d.ur_cstride, d.s_u = du.res1, du.r1_bstride, du.r1_cstride, du.s1
+        else:
+            d.s_u = 1.0
+        if not store_out:
+            d.y, d.y_bstride, d.y_cstride = 0, 0, 0
     d._flops = sum(x._flops for x in descs) + (head._flops if head is not None else 0.0)
     d._bytes = sum(x._bytes for x in descs)
     return d
@@ -1476,11 +1555,12 @@ class Engine:
                 bufs["gran"], self.status, res=bufs[f"V{top}"], res_scale=NF2, xcd=gru_xcd)
         # decoder (score.py:197-211)
         h = None
+        up_fused = False   # level l's up conv ran inside level l - 1's block (ou_block kEpiUp)
         for l in range(n_lvl):
             i = top - l
             bw = self.s_dec[l]
             prog.label = f"score dec L{i}"
-            if bw.kind == "up":
+            if bw.kind == "up" and not up_fused:
                 li = min(i, nr)
                 add_conv(prog, conv_desc(bw.rate_conv, h, bufs[f"V{i}"], n_frames=h.T,
                                          out_len=bufs["T"][li], valid_len=bw.rate * h.T,
@@ -1492,9 +1572,19 @@ class Engine:
             last = l == n_lvl - 1
             fuse_head = (last and head is not None and bw.fused is not None and bw.C in ENDS_C
                          and fuse_ends_enabled())
-            rec_block(prog, bw, bufs[f"V{i}"], bufs[f"A{i}"], bufs[f"A{i}"], bufs[f"B{i}"],
-                      film=fb(n_lvl + l), film_bs=film_bs, sc=sc_list[l], head=head if fuse_head else None)
+            # the next level's up conv reads only this block's output A{i}:
+            # where ou_block has the stage it runs inside this launch, adds
+            # the skip into V{i-1} in place, and A{i} is not stored at all
             h = bufs[f"A{i}"]
+            nxt = self.s_dec[l + 1] if l + 1 < n_lvl else None
+            up = None
+            if nxt is not None and nxt.kind == "up" and nxt.up is not None:
+                v = bufs[f"V{i - 1}"]
+                up = (nxt.up, conv_desc(nxt.rate_conv, h, v, n_frames=h.T, out_len=bufs["T"][min(i - 1, nr)],
+                                        valid_len=nxt.rate * h.T, res1=v, s1=NF2))
+            up_fused = rec_block(prog, bw, bufs[f"V{i}"], h, h, bufs[f"B{i}"],
+                                 film=fb(n_lvl + l), film_bs=film_bs, sc=sc_list[l],
+                                 head=head if fuse_head else None, up=up, store_out=False)
             if last and head is not None:
                 if not fuse_head:
                     head.h, head.h_bstride = h.ptr, h.bs

@@ -139,6 +139,9 @@ def _block(d):
         W.append(_box(d.e, 4 * d.e_bstride, 4 * d.e_cstride, d.batch, 2 * C, 4 * (f0 // r), 4 * (-(-f1 // r))))
     if d.sy:
         W.append(_box(d.sy, d.sy_bstride, 0, d.batch, 1, 0, (C // 32) * d.sy_rows * 128))
+    if d.w_up:   # the fused up-sampling conv: u (and its skip residual) over [0, u_len); y may be NULL
+        R.append(_box(d.u_res, 4 * d.ur_bstride, 4 * d.ur_cstride, d.batch, C // 2, 0, 4 * d.u_len))
+        W.append(_box(d.u, 4 * d.u_bstride, 4 * d.u_cstride, d.batch, C // 2, 0, 4 * d.u_len))
     return R, W
 
 
