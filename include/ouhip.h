@@ -492,7 +492,9 @@ typedef struct ou_block_desc {
     const float* res2;         /* or NULL                                        */
     int64_t r2_bstride, r2_cstride;
     int32_t* status;           /* split-f16 range flag (as ou_conv), or NULL     */
-    /* 32 channels only, the score network's ends (both optional, NULL = off):
+    /* 32 and 48 channels (the score network's level-0 blocks of PP16 / PP24;
+     * with w_down as well, 32 only), the score network's ends (both optional,
+     * NULL = off):
      * the block input is h = conv1d(in_scale[b] * x, w_in, b_in) (score
      * input_conv, 1 -> C, k3, score.py:244-246,285) instead of reading h;
      * and/or the block output goes through the score head (ou_head fields of

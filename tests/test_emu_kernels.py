@@ -187,6 +187,58 @@ def test_block_values_match_reference(tmp_path):
         assert p.returncode == 0 and "ok:" in out, (out[-2000:], err[-2000:])
 
 
+def test_block_values_ends_match_reference(tmp_path):
+    """The score network's ends in the same emulation (groups 6 .. 11 of
+    block_emu_values: 32 / 48 channels x f32 / split-f16 / f16): the fused
+    input conv (kEpiIn alone, with FiLM, with FiLM and the rate-change conv;
+    with and without in_scale) and the fused head (kEpiHead alone and in the
+    decoder form; modes 0 / 1 / 2, with and without the EDM wrapper, out
+    written over x, both PReLU slope signs) against double precision, batch 2,
+    at 1, 3, Fo + 1 and 2 Fo + 1 frames (Fo: the variant's owned frames),
+    with nothing stored outside the windows.  A test of its own: these
+    launches would double the run time of the groups above."""
+    exe = str(tmp_path / "block_emu_values")
+    _build("block_emu_values.cpp", exe, "-O0", "-DOU_EMU_FIBERS")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
+    procs = [subprocess.Popen([exe, str(g)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
+             for g in range(6, 12)]
+    for p in procs:
+        out, err = p.communicate(timeout=1200)
+        assert p.returncode == 0 and "ok:" in out, (out[-2000:], err[-2000:])
+
+
+END_MUTANTS = {
+    # the head's Y row outside [0, T) holds a value instead of the zero padding
+    "y_pad": ("Y[w * YS + row(mr, r)] = inside ? v : 0.f;", "Y[w * YS + row(mr, r)] = v;"),
+    # stage 0 of the fused input conv: h outside the clip is b_in instead of 0
+    "h_pad": ("                if (t < tlo || t >= thi || (d.dbg & 1)) {\n#pragma unroll\n"
+              "                    for (int i = 0; i < 8; ++i) v[it][i] = 0.f;",
+              "                if (false) {\n#pragma unroll\n"
+              "                    for (int i = 0; i < 8; ++i) v[it][i] = 0.f;"),
+    "in_scale": ("(d.in_scale ? d.in_scale[b] : 1.f)", "(1.f)"),
+    "prelu_order": ("                        v = v >= 0.f ? v : v * hd.slope1;\n"
+                    "                        v = v >= 0.f ? v : v * hd.slope2;",
+                    "                        v = v >= 0.f ? v : v * hd.slope2;\n"
+                    "                        v = v >= 0.f ? v : v * hd.slope1;"),
+    "z_item": ("hd.z[o]", "hd.z[t]"),
+}
+
+
+def test_block_values_ends_catch_wrong_values(tmp_path):
+    """The ends group bites: five one-line wrong-value edits of ou_block.hip
+    (none moves an address) each fail the 32-channel split-f16 group."""
+    procs = {}
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
+    for name, (old, new) in END_MUTANTS.items():
+        src = _mutant(tmp_path / name, "ou_block.hip", old, new)
+        exe = str(tmp_path / name / "block_emu_values")
+        _build("block_emu_values.cpp", exe, "-O0", "-DOU_EMU_FIBERS", f'-DOU_EMU_BLOCK_SRC="{src}"')
+        procs[name] = subprocess.Popen([exe, "7"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
+    for name, p in procs.items():
+        out, err = p.communicate(timeout=1200)
+        assert p.returncode == 1 and "FAIL:" in out and " 0 bad" not in out, (name, out[-2000:], err[-2000:])
+
+
 def test_split_image_values_match_reference(tmp_path):
     """Fiber emulation of the split-image path, under AddressSanitizer: the
     consumer kernel (OU_TILE_SS) against a double-precision evaluation at
