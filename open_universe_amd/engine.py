@@ -1114,28 +1114,11 @@ class ConvTuner:
             return tile & ~L.TILE_KS_MASK
         return tile
 
-    def __call__(self, d):
-        import ctypes
-        import os
-
-        k = self.key(d)
-        if k in self.cache:
-            return self.fit_workspace(d, self.cache[k])
-        # the same geometry tuned at another length: reuse its tile (nearest
-        # bucket) instead of timing every candidate again
-        g, b = self.geometry(d), self.bucket(d.n_frames)
-        near = self.by_geom.get(g)
-        if near and os.environ.get("OUHIP_TUNE_EVERY_LENGTH", "0") != "1":
-            bb = min(near, key=lambda x: (abs(x - b), x))
-            self.cache[k] = self.cache[g + (bb,)]
-            if g + (bb,) in self.times:   # another length's time: a rough figure, scaled by the frames
-                self.times[k] = self.times[g + (bb,)] * 2.0 ** (b - bb)
-            near.add(b)
-            return self.fit_workspace(d, self.cache[k])
+    @staticmethod
+    def candidates(d):
+        """Every tile word the tuner times for descriptor ``d`` (ou_conv may
+        still refuse one at launch: LDS, chunk count, workspace)."""
         lib = L.load()
-        stream = torch.cuda.current_stream().cuda_stream
-        best, best_ms = -1, float("inf")
-        self.timed += 1
         # tile shape x log2(output tiles per workgroup); > 0 = persistent kernel
         # (TILE_WS: the warp-specialised persistent kernel)
         # (split-f16, TILE_SPLIT_QUERY in the query only: one-tile workgroups)
@@ -1166,6 +1149,31 @@ class ConvTuner:
                      if lib.ou_conv_tile_ok(d.kt, t | v)]
             cands += [t | k for t in range(lib.ou_conv_num_tiles()) if lib.ou_conv_tile_ok(d.kt, t)
                       for k in ksl[1:]]
+        return cands
+
+    def __call__(self, d):
+        import ctypes
+        import os
+
+        k = self.key(d)
+        if k in self.cache:
+            return self.fit_workspace(d, self.cache[k])
+        # the same geometry tuned at another length: reuse its tile (nearest
+        # bucket) instead of timing every candidate again
+        g, b = self.geometry(d), self.bucket(d.n_frames)
+        near = self.by_geom.get(g)
+        if near and os.environ.get("OUHIP_TUNE_EVERY_LENGTH", "0") != "1":
+            bb = min(near, key=lambda x: (abs(x - b), x))
+            self.cache[k] = self.cache[g + (bb,)]
+            if g + (bb,) in self.times:   # another length's time: a rough figure, scaled by the frames
+                self.times[k] = self.times[g + (bb,)] * 2.0 ** (b - bb)
+            near.add(b)
+            return self.fit_workspace(d, self.cache[k])
+        lib = L.load()
+        stream = torch.cuda.current_stream().cuda_stream
+        best, best_ms = -1, float("inf")
+        self.timed += 1
+        cands = self.candidates(d)
         log = os.environ.get("OUHIP_TUNE_LOG")
         # candidates run on whatever the buffers hold at record time: keep
         # their split-f16 range flags out of the engine's status word (and

@@ -16,7 +16,9 @@ boxes overlap iff some (item, row, byte) of one equals one of the other,
 which is decided exactly per item offset (no layout assumptions).  Weights,
 biases and other recorded constants are never written during a replay and
 are left out.  Every plan schedule the package records is checked
-(tests/test_hazards.py)."""
+(tests/test_hazards.py), and the boxes themselves are checked against what
+the kernels read and write by stepping recorded plans on the GPU
+(tests/test_gpu_footprints.py): change a box only together with that test."""
 from dataclasses import dataclass
 
 from . import _lib as L
