@@ -944,6 +944,102 @@ int ou_model_enhance_long_noise(ou_model* m, const float* x, int64_t n, int over
 int ou_model_enhance_long(ou_model* m, const float* x, int64_t n, int overlap, float* out, uint64_t seed,
                           uint64_t offset, float* workspace, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Streaming enhance (ou_stream.hip; DESIGN.md section 15 has the definition,
+ * open_universe_amd/longform.py restates the arithmetic on the host).
+ *
+ * A stream is the windowed enhance above on the concatenation of everything
+ * pushed, run as the samples arrive.  With `fed` samples pushed, window i is
+ * regular, start i H, and may run as soon as fed >= i H + W; at close, T = fed,
+ * the window list is that of a clip of T samples, so only the last window can
+ * be shifted, and every window that ran earlier is a regular window of that
+ * list.  Windows run in groups [g B, g B + B); the windows left at close run as
+ * one last group whose unused slots repeat window n - 1.
+ *
+ * The noise is a function of position: sample t of draw k is element t of the
+ * ou_randn stream at (seed, offset + k 2^38) -- counter offset + k 2^38 +
+ * (t >> 2), lane t & 3 -- so it depends neither on T, nor on the grouping, nor
+ * on how the pushes were cut; window i uses samples [start(i), start(i) +
+ * noise_win) of every draw.  A draw has 2^40 samples: nothing may reach past.
+ *
+ * The caller keeps an input ring of `cap` >= W floats that holds the samples
+ * [lo, fed) of the stream, sample p at ring[p mod cap], and a carry of O
+ * floats.  Both calls describe their group as windows [first, first + count)
+ * and, with closing != 0, the stream's final length T (first + count must then
+ * be the window count of T; the start of the last window is min of its
+ * regular start and T - W).
+ *
+ * ou_stream_gather: for slot b < slots (<= 65535), s_b the start of window
+ * first + min(b, count - 1): mix[b mix_bstride + j] = ring[(s_b + j) mod cap],
+ * j < W, and for r < noise_rows: nz[r nz_rstride + b nz_bstride + j] = sample
+ * s_b + j of draw r, j < noise_win, generated in place with the code of
+ * ou_randn (bit-equal to a row of ou_randn sliced at s_b, whatever s_b mod 4
+ * is).  One launch per 32 slots.  Refused on the host: null pointers it uses,
+ * count < 1, slots < count, O outside [0, W / 2], cap < W, a ring range that
+ * is not 0 <= lo <= fed <= lo + cap, a window outside [lo, fed), closing with
+ * T != fed or with a window count that is not T's, strides smaller than a row,
+ * and noise past sample 2^40.
+ *
+ * ou_stream_overlap_add: emits the samples the group makes final, out[m] =
+ * sample first H + m of the stream for first H + m < (first + count) H, or
+ * < T when closing, and stores their number in *n_out (may be NULL).  Sample t
+ * belongs to window own = min(t / H, first + count - 1): 0 + 1 v outside the
+ * owner's fade-in, (0 + (1 - f) v_prev) + f v inside it, each "+ w v" one fused
+ * multiply-add, fma(f, v, fma(1 - f, v_prev, 0)) -- the bits ou_overlap_add
+ * gives on the device over the whole stream.  v_prev of
+ * window `first` is read from the carry; a call that is not closing then
+ * leaves the raw last O samples of window first + count - 1 in the carry.  A
+ * closing call with count = 0 -- every window has run and the last one ended
+ * at T -- emits the carry alone, with weight 1.  The groups must run in order
+ * from first = 0.  w holds window first + b at w + b w_bstride, W values; fade
+ * is ou_long_fade's table (NULL when O = 0, and then so may be the carry).  No
+ * sample is written twice and nothing needs clearing.  Refused on the host:
+ * null pointers it uses, O outside [0, W / 2], count < 1 unless closing,
+ * w_bstride < W, and a closing call whose T is shorter than W or does not
+ * have first + count windows.
+ * ---------------------------------------------------------------------- */
+int ou_stream_gather(const float* ring, int64_t cap, int64_t lo, int64_t fed, int window, int overlap, int64_t first,
+                     int count, int slots, int closing, int64_t T, int noise_rows, int64_t noise_win, uint64_t seed,
+                     uint64_t offset, float* mix, int64_t mix_bstride, float* nz, int64_t nz_rstride,
+                     int64_t nz_bstride, void* stream);
+int ou_stream_overlap_add(const float* w, int64_t w_bstride, int window, int overlap, int64_t first, int count,
+                          int closing, int64_t T, const float* fade, float* carry, float* out, int64_t* n_out,
+                          void* stream);
+
+/* A streaming session on a loaded bundle: W and B are the bundle's own; x and
+ * out are device pointers.  open allocates the ring (W + B H floats), the carry
+ * and the fade table; nothing allocates after it, and the memory does not grow
+ * with the stream.  push consumes n >= 0 samples -- any n, in pieces when it is
+ * more than the ring has room for -- runs every group that becomes ready
+ * (gather, replay, overlap-add, all on ``stream``) and writes the samples they
+ * make final to out, *n_out of them: after windows [0, m) have run, samples
+ * [0, m H) have been emitted, and the last O samples of window m - 1 wait for
+ * their successor.  close runs the windows that are left as one last group and
+ * emits everything up to T.  ou_model_stream_bound is the count push(n), or
+ * with closing != 0 close, would emit now: host arithmetic on the counts alone,
+ * no synchronisation (-1 with a message for a closing stream shorter than W).
+ * The concatenated output equals, bit for bit, ou_model_enhance_long_noise on
+ * the whole clip with draw k filled by ou_randn at (seed, offset + k 2^38), for
+ * every way of cutting the pushes; for T = W, ou_model_enhance_noise on B copies
+ * of the window, item 0.
+ *
+ * close on fewer than W samples fails with OU_STREAM_SHORT; the session stays
+ * valid and can be destroyed.  A stream that would pass 2^40 samples is
+ * refused.  One session at a time per model: its MIX, NZ and OUT buffers are
+ * the model's, so a second open, and every ou_model_enhance* call, is refused
+ * while one is open (destroy it first).  Use one stream for all calls of a
+ * session, or order them yourself.  ou_model_status applies as after
+ * ou_model_enhance: when it reports an error, the session has failed -- the
+ * next push or close returns that code and emits nothing.  Destroying the
+ * model destroys its open session.                                           */
+#define OU_STREAM_SHORT 3
+typedef struct ou_stream ou_stream;
+int ou_model_stream_open(ou_model* m, int overlap, uint64_t seed, uint64_t offset, ou_stream** out);
+int64_t ou_model_stream_bound(const ou_stream* s, int64_t n, int closing);
+int ou_model_stream_push(ou_stream* s, const float* x, int64_t n, float* out, int64_t* n_out, void* stream);
+int ou_model_stream_close(ou_stream* s, float* out, int64_t* n_out, void* stream);
+void ou_model_stream_destroy(ou_stream* s);
+
 #ifdef __cplusplus
 }
 #endif

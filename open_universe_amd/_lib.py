@@ -269,7 +269,18 @@ EXPORTS = {
     "ou_model_long_noise": (c_int64, [c_void_p, c_int64, c_int, POINTER(c_int64)]),
     "ou_model_enhance_long_noise": (c_int, [c_void_p, fp, c_int64, c_int, fp, fp, c_void_p]),
     "ou_model_enhance_long": (c_int, [c_void_p, fp, c_int64, c_int, fp, c_uint64, c_uint64, fp, c_void_p]),
+    "ou_stream_gather": (c_int, [fp, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_int, c_int, c_int, c_int64,
+                                 c_int, c_int64, c_uint64, c_uint64, fp, c_int64, fp, c_int64, c_int64, c_void_p]),
+    "ou_stream_overlap_add": (c_int, [fp, c_int64, c_int, c_int, c_int64, c_int, c_int, c_int64, fp, fp, fp,
+                                      POINTER(c_int64), c_void_p]),
+    "ou_model_stream_open": (c_int, [c_void_p, c_int, c_uint64, c_uint64, POINTER(c_void_p)]),
+    "ou_model_stream_bound": (c_int64, [c_void_p, c_int64, c_int]),
+    "ou_model_stream_push": (c_int, [c_void_p, fp, c_int64, fp, POINTER(c_int64), c_void_p]),
+    "ou_model_stream_close": (c_int, [c_void_p, fp, POINTER(c_int64), c_void_p]),
+    "ou_model_stream_destroy": (None, [c_void_p]),
 }
+
+STREAM_SHORT = 3   # OU_STREAM_SHORT: ou_model_stream_close on fewer samples than one window
 
 _lib = None
 

@@ -399,6 +399,11 @@ class Bundle:
                                                int(seed), int(offset), ws.data_ptr(), stream), "model_enhance_long")
         return out
 
+    def stream(self, overlap, seed=0, offset=0):
+        """A streaming session on this bundle (:class:`BundleStream`): one at
+        a time, and ``enhance*`` is refused while it is open."""
+        return BundleStream(self, overlap, seed, offset)
+
     def status(self):
         """Wait for the latest enhance and read the status words: 0 when it
         ran clean; raises OuHipError on a GRU hand-off timeout and
@@ -412,11 +417,98 @@ class Bundle:
 
     def close(self):
         if getattr(self, "h", None):
+            s = getattr(self, "_stream", None)
+            if s is not None:
+                s.release()
             self.lib.ou_model_destroy(self.h)
             self.h = None
 
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+class BundleStream:
+    """A streaming session through the C ABI (ou_model_stream_*; DESIGN.md
+    section 15): ``push(x) -> Tensor`` takes the next samples of the stream (a
+    CPU or device tensor, any length) and returns the samples that became final
+    on the device; ``close() -> Tensor`` returns the rest; ``bound(n)`` is the
+    count ``push`` of ``n`` samples would return, ``bound(closing=True)`` what
+    ``close`` would.  The window and the group size are the bundle's ``length``
+    and ``batch``.  A context manager: leaving it destroys the session.  Call
+    the bundle's ``status()`` before using what a push returned."""
+
+    def __init__(self, bundle, overlap, seed=0, offset=0):
+        self.bundle, self.lib = bundle, bundle.lib
+        self.h = c_void_p()
+        L.check(self.lib.ou_model_stream_open(bundle.h, int(overlap), int(seed), int(offset), ctypes.byref(self.h)),
+                "model_stream_open")
+        bundle._stream = self
+
+    def _raise(self, rc, what):
+        from .longform import StreamShort
+
+        msg = (self.lib.ou_last_error() or b"").decode()
+        if rc == L.STREAM_SHORT:
+            raise StreamShort(f"{what}: {msg}")
+        raise (L.OuRangeError if rc == 2 else L.OuHipError)(f"{what}: ouhip error {rc}: {msg}")
+
+    def bound(self, n=0, closing=False):
+        r = self.lib.ou_model_stream_bound(self.h, int(n), int(bool(closing)))
+        if r < 0:
+            self._raise(L.STREAM_SHORT if closing else int(r), "model_stream_bound")
+        return int(r)
+
+    def _out(self, n):
+        import torch
+
+        dev = torch.device("cuda", torch.cuda.current_device())
+        return torch.empty(n, dtype=torch.float32, device=dev), c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def push(self, x):
+        import torch
+
+        x = torch.as_tensor(x)
+        if x.ndim != 1 and x.numel() != x.shape[-1]:
+            raise ValueError("a stream is one mono signal: push (n,), (1, n) or (1, 1, n)")
+        out, stream = self._out(self.bound(x.numel()))
+        x = x.reshape(-1).to(device=out.device, dtype=torch.float32).contiguous()
+        got = ctypes.c_int64(0)
+        rc = self.lib.ou_model_stream_push(self.h, x.data_ptr() if x.numel() else 0, x.numel(),
+                                           out.data_ptr() if out.numel() else 0, ctypes.byref(got), stream)
+        if rc:
+            self._raise(rc, "model_stream_push")
+        assert got.value == out.numel(), (got.value, out.numel())
+        return out
+
+    def close(self):
+        n = self.lib.ou_model_stream_bound(self.h, 0, 1)
+        out, stream = self._out(max(int(n), 0))
+        got = ctypes.c_int64(0)
+        rc = self.lib.ou_model_stream_close(self.h, out.data_ptr() if out.numel() else 0, ctypes.byref(got), stream)
+        if rc:
+            self._raise(rc, "model_stream_close")
+        assert got.value == out.numel(), (got.value, out.numel())
+        return out
+
+    def release(self):
+        if getattr(self, "h", None):
+            self.lib.ou_model_stream_destroy(self.h)
+            self.h = None
+            if getattr(self.bundle, "_stream", None) is self:
+                self.bundle._stream = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+    def __del__(self):
+        try:
+            self.release()
         except Exception:
             pass

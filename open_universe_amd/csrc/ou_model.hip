@@ -13,6 +13,19 @@
 #include "../../include/ouhip.h"
 #include "ou_common.h"
 
+// a streaming session (ou_model_stream_*): the stream's state on the device --
+// the input ring, the crossfade carry, the fade table -- and its counts
+struct ou_stream {
+    ou_model* m = nullptr;
+    int W = 0, B = 0, Tp = 0, O = 0, rows = 0;
+    long long H = 0, cap = 0;
+    uint64_t seed = 0, offset = 0;
+    long long fed = 0, run = 0;   // samples pushed; windows run, a multiple of B until close
+    bool closed = false;
+    int failed = 0;               // the code ou_model_status reported: every later call returns it
+    float *ring = nullptr, *carry = nullptr, *fade = nullptr;
+};
+
 struct ou_model {
     ou_bundle* bundle = nullptr;
     ou_bundle_meta meta{};
@@ -28,6 +41,7 @@ struct ou_model {
     float* fade = nullptr;
     int fade_overlap = -1;
     std::vector<float> fade_host;
+    ou_stream* live = nullptr;   // the open streaming session: it owns mix, noise and out until destroyed
 };
 
 namespace {
@@ -151,6 +165,35 @@ int long_run(ou_model* m, const float* x, int64_t n, int overlap, const float* n
     return 0;
 }
 
+constexpr long long kStreamMaxSamples = 1LL << 40;
+
+// windows of a stream that are regular and whose samples are all there
+long long stream_ready(const ou_stream* s, long long fed) { return fed < s->W ? 0 : (fed - s->W) / s->H + 1; }
+
+// windows [first, first + count) as one group: gather, replay, overlap-add, all on st
+int stream_group(ou_stream* s, long long first, int count, int closing, float* out, int64_t* n_out, hipStream_t st)
+{
+    ou_model* m = s->m;
+    const long long lo = s->fed > s->cap ? s->fed - s->cap : 0;
+    int rc = 0;
+    if (count > 0) {
+        if ((rc = ou_stream_gather(s->ring, s->cap, lo, s->fed, s->W, s->O, first, count, s->B, closing, s->fed,
+                                   s->rows, s->Tp, s->seed, s->offset, m->mix, s->W, m->noise,
+                                   (int64_t)s->B * s->Tp, s->Tp, st)))
+            return rc;
+        if ((rc = m->captured ? ou_program_launch(m->prog, st) : ou_program_run(m->prog, st))) return rc;
+    }
+    return ou_stream_overlap_add(m->out, s->W, s->W, s->O, first, count, closing, s->fed,
+                                 s->O > 0 ? s->fade : nullptr, s->carry, out, n_out, st);
+}
+
+int stream_usable(const ou_stream* s, const char* what)
+{
+    if (s->failed) return ou_fail(s->failed, "%s: the session failed (ou_model_status reported %d)", what, s->failed);
+    if (s->closed) return ou_fail(-1, "%s: the session is closed", what);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -158,6 +201,7 @@ extern "C" {
 void ou_model_destroy(ou_model* m)
 {
     if (!m) return;
+    if (m->live) ou_model_stream_destroy(m->live);
     (void)hipDeviceSynchronize();   // nothing of it may still run when its memory goes
     if (m->prog) ou_program_destroy(m->prog);
     for (void* p : m->regions)
@@ -184,6 +228,7 @@ int ou_bundle_load(const char* path, int capture, ou_model** out)
 int ou_model_enhance_noise(ou_model* m, const float* mix, const float* noise, float* out, void* stream)
 {
     if (!m || !mix || !noise || !out) return ou_fail(-1, "model_enhance_noise: null");
+    if (m->live) return ou_fail(-1, "model_enhance_noise: a streaming session is open on this model");
     hipStream_t s = (hipStream_t)stream;
     int rc = copy_mix(m, mix, s);
     if (rc) return rc;
@@ -195,6 +240,7 @@ int ou_model_enhance_noise(ou_model* m, const float* mix, const float* noise, fl
 int ou_model_enhance(ou_model* m, const float* mix, float* out, uint64_t seed, uint64_t offset, void* stream)
 {
     if (!m || !mix || !out) return ou_fail(-1, "model_enhance: null");
+    if (m->live) return ou_fail(-1, "model_enhance: a streaming session is open on this model");
     hipStream_t s = (hipStream_t)stream;
     int rc = copy_mix(m, mix, s);
     if (rc) return rc;
@@ -216,6 +262,7 @@ int ou_model_enhance_long_noise(ou_model* m, const float* x, int64_t n, int over
                                 float* out, void* stream)
 {
     if (!m || !x || !noise || !out) return ou_fail(-1, "model_enhance_long_noise: null");
+    if (m->live) return ou_fail(-1, "model_enhance_long_noise: a streaming session is open on this model");
     int64_t n_win = 0, len = 0;
     const int rc = long_check(m, "model_enhance_long_noise", n, overlap, &n_win, &len);
     if (rc) return rc;
@@ -226,6 +273,7 @@ int ou_model_enhance_long(ou_model* m, const float* x, int64_t n, int overlap, f
                           uint64_t offset, float* workspace, void* stream)
 {
     if (!m || !x || !out || !workspace) return ou_fail(-1, "model_enhance_long: null");
+    if (m->live) return ou_fail(-1, "model_enhance_long: a streaming session is open on this model");
     int64_t n_win = 0, len = 0;
     int rc = long_check(m, "model_enhance_long", n, overlap, &n_win, &len);
     if (rc) return rc;
@@ -246,6 +294,7 @@ int ou_model_status(ou_model* m)
     if (!any) return 0;
     OU_HIP_CHECK(hipMemsetAsync(m->status, 0, n, m->last), "model_status: clear");
     OU_HIP_CHECK(hipStreamSynchronize(m->last), "model_status: sync");
+    if (m->live) m->live->failed = m->status_host[0] ? 1 : 2;
     if (m->status_host[0]) return ou_fail(1, "GRU recurrence timed out (workgroup hand-off never completed)");
     return ou_fail(2, "split-f16 operand out of range: use a bundle exported with f32 operands");
 }
@@ -255,6 +304,120 @@ int ou_model_info(const ou_model* m, ou_bundle_meta* meta)
     if (!m || !meta) return ou_fail(-1, "model_info: null");
     *meta = m->meta;
     return 0;
+}
+
+int ou_model_stream_open(ou_model* m, int overlap, uint64_t seed, uint64_t offset, ou_stream** out)
+{
+    if (!m || !out) return ou_fail(-1, "model_stream_open: null");
+    *out = nullptr;
+    if (m->live) return ou_fail(-1, "model_stream_open: a streaming session is already open on this model");
+    const int W = m->meta.mix.length;
+    if (overlap < 0 || overlap > W / 2)
+        return ou_fail(-1, "model_stream_open: overlap %d outside [0, window / 2] = [0, %d]", overlap, W / 2);
+    ou_stream* s = new ou_stream();
+    s->m = m;
+    s->W = W, s->B = m->meta.mix.batch, s->Tp = m->meta.noise.length, s->O = overlap, s->rows = m->meta.noise.count;
+    s->H = W - overlap;
+    s->cap = W + s->B * s->H;
+    s->seed = seed, s->offset = offset;
+    std::vector<float> tab(2 * (size_t)overlap + 1, 0.f);
+    int rc = ou_long_fade(overlap, tab.data());
+    hipError_t e = hipSuccess;
+    if (!rc && (e = hipMalloc((void**)&s->ring, 4ull * (size_t)s->cap)) != hipSuccess) rc = -1;
+    if (!rc && (e = hipMalloc((void**)&s->carry, 4ull * (size_t)(overlap + 1))) != hipSuccess) rc = -1;
+    if (!rc && (e = hipMalloc((void**)&s->fade, 4ull * (2 * (size_t)overlap + 1))) != hipSuccess) rc = -1;
+    if (!rc && (e = hipMemcpy(s->fade, tab.data(), 4ull * (2 * (size_t)overlap + 1), hipMemcpyHostToDevice)) != hipSuccess)
+        rc = -1;
+    if (rc) {
+        if (e != hipSuccess) ou_fail(-1, "model_stream_open: %s", hipGetErrorString(e));
+        ou_model_stream_destroy(s);
+        return rc;
+    }
+    m->live = s;
+    *out = s;
+    return 0;
+}
+
+int64_t ou_model_stream_bound(const ou_stream* s, int64_t n, int closing)
+{
+    if (!s || n < 0) return ou_fail(-1, "model_stream_bound: bad arguments");
+    if (s->failed || s->closed) return 0;
+    if (closing) {
+        if (s->fed < s->W)
+            return ou_fail(-1, "model_stream_bound: a stream of %lld samples is shorter than one window of %d",
+                           s->fed, s->W);
+        return s->fed - s->run * s->H;
+    }
+    const long long ready = stream_ready(s, s->fed + n);
+    return (ready - s->run) / s->B * s->B * s->H;
+}
+
+int ou_model_stream_push(ou_stream* s, const float* x, int64_t n, float* out, int64_t* n_out, void* stream)
+{
+    if (!s || n < 0 || (n > 0 && !x)) return ou_fail(-1, "model_stream_push: bad arguments");
+    if (n_out) *n_out = 0;
+    int rc = stream_usable(s, "model_stream_push");
+    if (rc) return rc;
+    if (s->fed + n + (s->Tp - s->W) > kStreamMaxSamples)
+        return ou_fail(-1, "model_stream_push: the stream would pass 2^40 samples");
+    if (ou_model_stream_bound(s, n, 0) > 0 && !out) return ou_fail(-1, "model_stream_push: null output");
+    hipStream_t st = (hipStream_t)stream;
+    s->m->last = st;
+    long long left = n, total = 0;
+    for (;;) {
+        while (stream_ready(s, s->fed) - s->run >= s->B) {
+            int64_t got = 0;
+            if ((rc = stream_group(s, s->run, s->B, 0, out + total, &got, st))) return rc;
+            s->run += s->B;
+            total += got;
+            if (n_out) *n_out = total;
+        }
+        if (left == 0) break;
+        // the ring keeps [min(run H, fed - W), fed): the next window's samples, and the last W for a shifted close
+        long long keep = s->run * s->H < s->fed - s->W ? s->run * s->H : s->fed - s->W;
+        if (keep < 0) keep = 0;
+        const long long room = s->cap - (s->fed - keep);
+        if (room <= 0) return ou_fail(-1, "model_stream_push: the ring is full with no group ready");
+        const long long take = left < room ? left : room;
+        const long long at = s->fed % s->cap;
+        const long long head = take < s->cap - at ? take : s->cap - at;
+        OU_HIP_CHECK(hipMemcpyAsync(s->ring + at, x, 4ull * (size_t)head, hipMemcpyDeviceToDevice, st),
+                     "model_stream_push: copy in");
+        if (take > head)
+            OU_HIP_CHECK(hipMemcpyAsync(s->ring, x + head, 4ull * (size_t)(take - head), hipMemcpyDeviceToDevice, st),
+                         "model_stream_push: copy in");
+        s->fed += take, x += take, left -= take;
+    }
+    return 0;
+}
+
+int ou_model_stream_close(ou_stream* s, float* out, int64_t* n_out, void* stream)
+{
+    if (!s) return ou_fail(-1, "model_stream_close: null");
+    if (n_out) *n_out = 0;
+    int rc = stream_usable(s, "model_stream_close");
+    if (rc) return rc;
+    if (s->fed < s->W)
+        return ou_fail(OU_STREAM_SHORT, "model_stream_close: a stream of %lld samples is shorter than one window of %d",
+                       s->fed, s->W);
+    const long long n = 1 + (s->fed - s->W + s->H - 1) / s->H;
+    if (s->fed - s->run * s->H > 0 && !out) return ou_fail(-1, "model_stream_close: null output");
+    s->m->last = (hipStream_t)stream;
+    if ((rc = stream_group(s, s->run, (int)(n - s->run), 1, out, n_out, (hipStream_t)stream))) return rc;
+    s->run = n;
+    s->closed = true;
+    return 0;
+}
+
+void ou_model_stream_destroy(ou_stream* s)
+{
+    if (!s) return;
+    (void)hipDeviceSynchronize();   // nothing of it may still run when its memory goes
+    if (s->ring) (void)hipFree(s->ring);
+    if (s->carry) (void)hipFree(s->carry);
+    if (s->fade) (void)hipFree(s->fade);
+    if (s->m && s->m->live == s) s->m->live = nullptr;
+    delete s;
 }
 
 }  // extern "C"

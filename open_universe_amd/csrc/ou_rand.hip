@@ -11,20 +11,9 @@
 
 #include "../../include/ouhip.h"
 #include "ou_common.h"
-#include "ou_philox.h"
+#include "ou_normal.h"
 
 namespace {
-
-__device__ __forceinline__ void box_muller(uint32_t xa, uint32_t xb, float& za, float& zb)
-{
-    const float u1 = (float)((xa >> 8) + 1u) * 0x1p-24f;   // (0, 1], exact
-    const float u2 = (float)(xb >> 8) * 0x1p-24f;          // [0, 1), exact
-    const float r = sqrtf(-2.0f * logf(u1));
-    float s, c;
-    sincospif(2.0f * u2, &s, &c);
-    za = r * c;
-    zb = r * s;
-}
 
 // kVec: out is 16-byte aligned (one float4 store per counter)
 template <bool kVec>
@@ -34,14 +23,8 @@ __global__ void __launch_bounds__(256) randn_kernel(float* __restrict__ out, lon
     const long long nq = (n + 3) / 4;
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += stride) {
-        const unsigned long long cq = offset + (unsigned long long)q;
-        const uint32_t ctr[4] = {(uint32_t)cq, (uint32_t)(cq >> 32), 0u, 0u};
-        const uint32_t key[2] = {k0, k1};
-        uint32_t x[4];
-        ouhip_detail::philox4x32(ctr, key, x);
         float z[4];
-        box_muller(x[0], x[1], z[0], z[1]);
-        box_muller(x[2], x[3], z[2], z[3]);
+        ouhip_detail::normal4(k0, k1, offset + (unsigned long long)q, z);
         const long long i = 4 * q;
         if (kVec && i + 4 <= n) {
             *reinterpret_cast<float4*>(out + i) = make_float4(z[0], z[1], z[2], z[3]);

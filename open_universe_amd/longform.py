@@ -50,8 +50,33 @@ of its group, evaluated per sample in float32 as ``(0 + w_{i-1} v_{i-1}) +
 w_i v_i``, each product and sum rounded -- so ``y_c`` depends on the ``out``
 values alone, not on where the group boundaries fall.  For one clip this is
 ``enhance_long`` itself: the same slots, the same replays, the same bits.
+
+Streams (``Universe.stream``, ``bundle.Bundle.stream``, csrc/ou_stream.hip;
+DESIGN.md section 15).  A stream is the windowed enhance of the concatenation
+of everything pushed, ``B`` fixed.  With ``fed`` samples pushed, window ``i`` is
+regular (``start_i = i H``) and ready once ``fed >= i H + W``; group ``g`` --
+windows ``[g B, g B + B)`` -- runs when all of them are ready.  At close,
+``T = fed``: the window list is the one above for ``T``, the windows that have
+not run yet run as one last group (unused slots repeat window ``n - 1``), and
+only window ``n - 1`` can be shifted, so every window that ran before close is
+a regular window of the final list.  After windows ``[0, m)`` have run, the
+samples ``[0, m H)`` are final and have been emitted; the last ``O`` samples of
+window ``m - 1`` wait, raw, for their successor; close emits everything up to
+``T``.  ``T < W`` at close is an error of its own (nothing has run).  The
+noise is a function of position: sample ``t`` of draw ``k`` is element ``t`` of
+the native stream (ou_randn) at ``(seed, offset + k 2^38)``, counters of four
+samples, so a draw has ``2^40`` samples and a stream may not pass them; window
+``i`` uses samples ``[start_i, start_i + Tp)`` of every draw, whatever ``T``,
+the grouping or the cuts of the pushes are.  The input lives in a ring of
+``W + B H`` samples, position ``p`` at ``p mod capacity``, which must retain
+``[min(m H, fed - W), fed)``: the next window's samples, and the last ``W`` for
+a shifted last window, which starts before ``m H``.  :class:`StreamCounts`
+is that arithmetic.
 """
 import numpy as np
+
+DRAW_COUNTERS = 1 << 38         # Philox counters between two draws of a stream
+STREAM_MAX_SAMPLES = 1 << 40    # samples of one draw
 
 
 def check(T, W, O):
@@ -198,3 +223,100 @@ def overlap_add_pooled(outs, Ts, W, O, batch):
             seen[c][t] = True
             ys[c][t] = val.astype(f32)
     return ys
+
+
+def stream_draw_offset(offset, k):
+    """Counter offset of draw ``k`` of a stream opened at ``offset`` (64-bit)."""
+    return (int(offset) + int(k) * DRAW_COUNTERS) & 0xFFFFFFFFFFFFFFFF
+
+
+def stream_ring(W, O, B):
+    """Capacity of a stream's input ring in samples."""
+    return int(W) + int(B) * (int(W) - int(O))
+
+
+class StreamShort(ValueError):
+    """A stream was closed on fewer samples than one window."""
+
+
+class StreamCounts:
+    """The host arithmetic of one stream: ``fed`` samples pushed, ``run``
+    windows run.  ``push(n)`` and ``close()`` list the steps a session takes --
+    ``("feed", k)``: copy the next ``k`` samples into the ring at ``fed mod
+    capacity``; ``("group", first, count, closing)``: run windows ``[first,
+    first + count)`` (``count = 0``: emit the carry alone) -- and advance the
+    counts as the list is built; ``bound`` is the number of samples those steps
+    emit.  Nothing here depends on the device."""
+
+    def __init__(self, W, O, B, Tp=None):
+        _, self.W, self.O = check(1, W, O)
+        if int(B) < 1:
+            raise ValueError(f"batch must be at least 1, got {B}")
+        self.B, self.H = int(B), self.W - self.O
+        self.Tp = self.W if Tp is None else int(Tp)
+        self.cap = stream_ring(self.W, self.O, self.B)
+        self.fed = self.run = 0
+        self.closed = False
+
+    def ready(self, fed=None):
+        """Regular windows whose samples are all there."""
+        fed = self.fed if fed is None else fed
+        return 0 if fed < self.W else (fed - self.W) // self.H + 1
+
+    def retain(self):
+        """The lowest position the ring must still hold."""
+        return max(0, min(self.run * self.H, self.fed - self.W))
+
+    def held(self):
+        """The lowest position the ring does hold: it is never cleared."""
+        return max(0, self.fed - self.cap)
+
+    def bound(self, n=0, closing=False):
+        """Samples ``push(n)`` would emit now, or ``close()`` with ``closing``."""
+        if n < 0:
+            raise ValueError(f"a push of {n} samples")
+        if self.closed:
+            return 0
+        if closing:
+            if self.fed < self.W:
+                raise StreamShort(f"a stream of {self.fed} samples is shorter than one window of {self.W}")
+            return self.fed - self.run * self.H
+        return (self.ready(self.fed + n) - self.run) // self.B * self.B * self.H
+
+    def push(self, n):
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"a push of {n} samples")
+        if self.closed:
+            raise ValueError("the stream is closed")
+        if self.fed + n + self.Tp - self.W > STREAM_MAX_SAMPLES:
+            raise ValueError("the stream would pass 2^40 samples")
+        steps = []
+        while True:
+            while self.ready() - self.run >= self.B:
+                steps.append(("group", self.run, self.B, False))
+                self.run += self.B
+            if n == 0:
+                return steps
+            room = self.cap - (self.fed - self.retain())
+            assert room > 0, "the ring is full with no group ready"
+            k = min(n, room)
+            steps.append(("feed", k))
+            self.fed += k
+            n -= k
+
+    def close(self):
+        if self.closed:
+            raise ValueError("the stream is closed")
+        if self.fed < self.W:
+            raise StreamShort(f"a stream of {self.fed} samples is shorter than one window of {self.W}")
+        n = n_windows(self.fed, self.W, self.O)
+        steps = [("group", self.run, n - self.run, True)]
+        self.run, self.closed = n, True
+        return steps
+
+    @staticmethod
+    def emitted(step, H, T=None):
+        """Samples a ``group`` step emits (``T``: the length at close)."""
+        _, first, count, closing = step
+        return (T if closing else (first + count) * H) - first * H

@@ -454,6 +454,31 @@ class Universe(nn.Module):
         out = torch.stack(outs)
         return out[0] if mix.ndim == 1 else out if mix.ndim == 2 else out[:, None, :]
 
+    def stream(self, window: int, overlap: int, batch: int = 1, n_steps: Optional[int] = None,
+               epsilon: Optional[float] = None, keep_rms: Optional[bool] = False, seed: int = 0, offset: int = 0,
+               **unsupported):
+        """A streaming session (opt-in; stream.ModelStream, DESIGN.md section
+        15): ``push(x)`` takes the next samples of one mono signal at
+        ``self.fs`` and returns the samples that became final, ``close()``
+        returns the rest.  The stream is ``enhance_long`` of everything
+        pushed, on the ``(batch, window)`` plan ``enhance`` would record, a
+        window running as soon as its samples are there; ``batch = 1`` is the
+        low-latency case.  The noise is the native stream (ou_randn) at
+        ``(seed, offset + k 2^38)`` for draw ``k``, a function of position, so
+        the output depends neither on the stream's length nor on how the
+        pushes were cut.  ``target``, ``use_aux_signal``, ``ensemble`` and
+        ``warm_start`` are refused, as in ``enhance_long``."""
+        from ...stream import ModelStream
+
+        for k, v in unsupported.items():
+            if k in ("target", "fake_score_snr", "use_aux_signal", "ensemble", "ensemble_stat", "warm_start"):
+                if v is not None and v is not False and not (k == "ensemble_stat" and v == "median"):
+                    raise NotImplementedError(f"stream does not support {k}")
+            else:
+                raise TypeError(f"stream() got an unexpected keyword argument {k!r}")
+        return ModelStream(self, window, overlap, batch=batch, n_steps=n_steps, epsilon=epsilon, keep_rms=keep_rms,
+                           seed=seed, offset=offset)
+
     def enhance_long_many(self, mixes, window: int, overlap: int, batch: int = 8, n_steps: Optional[int] = None,
                           epsilon: Optional[float] = None, rng: Optional[torch.Generator] = None,
                           keep_rms: Optional[bool] = False, pre_noise=None, **unsupported):
