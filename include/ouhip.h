@@ -1040,6 +1040,106 @@ int ou_model_stream_push(ou_stream* s, const float* x, int64_t n, float* out, in
 int ou_model_stream_close(ou_stream* s, float* out, int64_t* n_out, void* stream);
 void ou_model_stream_destroy(ou_stream* s);
 
+/* ------------------------------------------------------------------------
+ * Multiplexed streams (ou_mux.hip; DESIGN.md section 16 has the definition,
+ * longform.MuxCounts the host arithmetic).
+ *
+ * C channels are streams as above, each with its own ring, carry, counts and
+ * (seed, offset); W, O and H are shared.  The windows that are ready run
+ * together in the slots of one batch-B plan: the slot list is [(c, i) for c
+ * ascending for i pending in c], group g its slots [g B, g B + B), the unused
+ * slots of the last group repeating its last real slot.  The rings are one
+ * buffer, channel c's at rings + c cap; the carries one buffer, channel c's at
+ * carries + c carry_stride.  Both calls keep no state and allocate nothing.
+ *
+ * ou_mux_gather: for slot b < n_slots (<= 65535) with channel c, start s and
+ * the held range [lo, fed) of c's ring: mix[b mix_bstride + j] = rings[c cap +
+ * (s + j) mod cap], j < W, and for r < noise_rows: nz[r nz_rstride + b
+ * nz_bstride + j] = sample s + j of draw r of the ou_randn stream at (seed,
+ * offset + r 2^38), j < noise_win -- per slot what ou_stream_gather gives for
+ * that channel alone, bit for bit.  A padding slot is an ordinary entry that
+ * names a window again.  One launch per 32 slots.  Refused on the host: null
+ * pointers it uses, n_slots < 1, cap < W, a channel outside [0, channels), a
+ * ring range that is not 0 <= lo <= fed <= lo + cap, a window outside [lo,
+ * fed), strides smaller than a row, and noise past sample 2^40.
+ *
+ * ou_mux_overlap_add: a run is a maximal stretch of consecutive slots of one
+ * channel in the group, windows [first, first + count) in the slots [slot, slot
+ * + count) of w (slot b at w + b w_bstride), with ou_stream_overlap_add's
+ * closing and T.  For every run the call emits to out + out_off what
+ * ou_stream_overlap_add(w + slot w_bstride, ..., carries + channel
+ * carry_stride, out + out_off) emits, bit for bit, and leaves the same carry;
+ * n_out[r] (may be NULL) is run r's count.  A run with count = 0 is a closing
+ * channel that has nothing left to run: it emits its carry alone.  Slots that
+ * belong to no run (padding) are not read, and write nothing.  One launch per
+ * 32 runs.  Refused on the host: what ou_stream_overlap_add refuses for a run;
+ * n_runs < 1; slots outside [0, n_slots) or not ascending from run to run;
+ * channels outside [0, channels) or not strictly ascending (a channel has one
+ * run in a group, so no two runs share a carry); outputs that are not ascending
+ * without overlap inside [0, out_len); carry_stride < O.
+ * ---------------------------------------------------------------------- */
+typedef struct ou_mux_slot {
+    int64_t start;        /* of the window, in the channel's stream */
+    int64_t lo, fed;      /* the channel's ring holds [lo, fed) */
+    uint64_t seed, offset;
+    int32_t channel, reserved;
+} ou_mux_slot;
+typedef struct ou_mux_run {
+    int64_t first, T;     /* T is read only when closing */
+    int64_t out_off;      /* where the run's samples go in out */
+    int32_t count, closing;
+    int32_t slot;         /* of window `first` in w */
+    int32_t channel;
+} ou_mux_run;
+int ou_mux_gather(const float* rings, int64_t cap, int channels, int window, const ou_mux_slot* slots, int n_slots,
+                  int noise_rows, int64_t noise_win, float* mix, int64_t mix_bstride, float* nz, int64_t nz_rstride,
+                  int64_t nz_bstride, void* stream);
+int ou_mux_overlap_add(const float* w, int64_t w_bstride, int n_slots, int window, int overlap,
+                       const ou_mux_run* runs, int n_runs, const float* fade, float* carries, int64_t carry_stride,
+                       int channels, float* out, int64_t out_len, int64_t* n_out, void* stream);
+
+/* A mux session on a loaded bundle: W and B are the bundle's own; samples and
+ * out are device pointers.  open allocates `channels` rings (W + B H floats
+ * each), `channels` carries and the fade table; no device memory is allocated
+ * after it, and the memory does not grow with the streams.
+ *
+ * channel_open takes a free channel (channel < 0: the lowest free one; the
+ * index goes to *opened, may be NULL) with its (seed, offset), so a service can
+ * reuse channels as calls come and go.  push copies n samples into the
+ * channel's ring on ``stream`` and never replays; more than ou_model_mux_room
+ * -- cap - (fed - retain), host arithmetic -- is refused whole and consumes
+ * nothing: call run first.  close marks the channel closing; on fewer than W
+ * samples it fails with OU_STREAM_SHORT for that channel only, which stays
+ * open.  A closing channel is free again when run has emitted its last samples.
+ *
+ * run pools the windows that are ready by the slot rule above, one
+ * ou_mux_gather, one replay and one ou_mux_overlap_add per group, all on
+ * ``stream``; with full_only != 0 only whole groups run and the rest wait.
+ * Channel c's samples land at out + offsets[c], n_out[c] of them (n_out has
+ * `channels` entries, may be NULL); ou_model_mux_bound gives those counts and
+ * offsets beforehand from the counts alone, no synchronisation, so out can be
+ * sized before the call.  Per channel the output is that of an
+ * ou_model_stream_* session whose groups are the mux's: y[t] = sum_i
+ * weight_i(t) out_i[t - start_i] with out_i what the plan returns for that
+ * window in the slot it ran in.
+ *
+ * One session at a time per model: a mux and a streaming session exclude each
+ * other, and every ou_model_enhance* call is refused while a mux is open
+ * (destroy it first).  Use one stream for all calls of a session, or order
+ * them yourself.  ou_model_status applies as after ou_model_enhance: when it
+ * reports an error, or when a run fails, the mux has failed as a whole and
+ * every later call returns the code.  Destroying the model destroys its open
+ * mux.                                                                       */
+typedef struct ou_mux ou_mux;
+int ou_model_mux_open(ou_model* m, int overlap, int channels, ou_mux** out);
+int ou_model_mux_channel_open(ou_mux* x, int channel, uint64_t seed, uint64_t offset, int* opened);
+int64_t ou_model_mux_room(const ou_mux* x, int channel);
+int ou_model_mux_push(ou_mux* x, int channel, const float* samples, int64_t n, void* stream);
+int ou_model_mux_close(ou_mux* x, int channel);
+int ou_model_mux_bound(const ou_mux* x, int full_only, int64_t* counts, int64_t* offsets);
+int ou_model_mux_run(ou_mux* x, int full_only, float* out, int64_t* n_out, void* stream);
+void ou_model_mux_destroy(ou_mux* x);
+
 #ifdef __cplusplus
 }
 #endif

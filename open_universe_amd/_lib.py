@@ -278,7 +278,31 @@ EXPORTS = {
     "ou_model_stream_push": (c_int, [c_void_p, fp, c_int64, fp, POINTER(c_int64), c_void_p]),
     "ou_model_stream_close": (c_int, [c_void_p, fp, POINTER(c_int64), c_void_p]),
     "ou_model_stream_destroy": (None, [c_void_p]),
+    "ou_model_mux_open": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
+    "ou_model_mux_channel_open": (c_int, [c_void_p, c_int, c_uint64, c_uint64, POINTER(c_int)]),
+    "ou_model_mux_room": (c_int64, [c_void_p, c_int]),
+    "ou_model_mux_push": (c_int, [c_void_p, c_int, fp, c_int64, c_void_p]),
+    "ou_model_mux_close": (c_int, [c_void_p, c_int]),
+    "ou_model_mux_bound": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "ou_model_mux_run": (c_int, [c_void_p, c_int, fp, POINTER(c_int64), c_void_p]),
+    "ou_model_mux_destroy": (None, [c_void_p]),
+    "ou_mux_gather": (c_int, [fp, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_int64, fp, c_int64, fp, c_int64,
+                              c_int64, c_void_p]),
+    "ou_mux_overlap_add": (c_int, [fp, c_int64, c_int, c_int, c_int, c_void_p, c_int, fp, fp, c_int64, c_int, fp,
+                                   c_int64, POINTER(c_int64), c_void_p]),
 }
+
+
+
+class MuxSlot(ctypes.Structure):   # ou_mux_slot
+    _fields_ = [("start", c_int64), ("lo", c_int64), ("fed", c_int64), ("seed", c_uint64), ("offset", c_uint64),
+                ("channel", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MuxRun(ctypes.Structure):    # ou_mux_run
+    _fields_ = [("first", c_int64), ("T", c_int64), ("out_off", c_int64), ("count", ctypes.c_int32),
+                ("closing", ctypes.c_int32), ("slot", ctypes.c_int32), ("channel", ctypes.c_int32)]
+
 
 STREAM_SHORT = 3   # OU_STREAM_SHORT: ou_model_stream_close on fewer samples than one window
 

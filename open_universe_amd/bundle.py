@@ -404,6 +404,12 @@ class Bundle:
         a time, and ``enhance*`` is refused while it is open."""
         return BundleStream(self, overlap, seed, offset)
 
+    def stream_mux(self, overlap, channels):
+        """A mux session on this bundle (:class:`BundleMux`): ``channels``
+        streams share the slots of its plan.  One session at a time -- a mux
+        or a stream -- and ``enhance*`` is refused while it is open."""
+        return BundleMux(self, overlap, channels)
+
     def status(self):
         """Wait for the latest enhance and read the status words: 0 when it
         ran clean; raises OuHipError on a GRU hand-off timeout and
@@ -417,9 +423,9 @@ class Bundle:
 
     def close(self):
         if getattr(self, "h", None):
-            s = getattr(self, "_stream", None)
-            if s is not None:
-                s.release()
+            for s in (getattr(self, "_stream", None), getattr(self, "_mux", None)):
+                if s is not None:
+                    s.release()
             self.lib.ou_model_destroy(self.h)
             self.h = None
 
@@ -499,6 +505,98 @@ class BundleStream:
             self.h = None
             if getattr(self.bundle, "_stream", None) is self:
                 self.bundle._stream = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class BundleMux:
+    """A mux session through the C ABI (ou_model_mux_*),
+    with the interface of ``mux.ModelMux``: ``open(seed, offset, channel) ->
+    c``, ``room(c)``, ``push(c, x)`` (a CPU or device tensor of at most
+    ``room(c)`` samples), ``close(c)``, ``run(full_only) ->`` one device tensor
+    per channel (views of one buffer), ``bound(full_only) -> (counts,
+    offsets)``.  The window and the batch are the bundle's ``length`` and
+    ``batch``.  A context manager: leaving it destroys the session.  Call the
+    bundle's ``status()`` before using what a run returned."""
+
+    def __init__(self, bundle, overlap, channels):
+        self.bundle, self.lib, self.channels = bundle, bundle.lib, int(channels)
+        self.h = c_void_p()
+        L.check(self.lib.ou_model_mux_open(bundle.h, int(overlap), self.channels, ctypes.byref(self.h)),
+                "model_mux_open")
+        bundle._mux = self
+
+    def _check(self, rc, what):
+        from .longform import StreamShort
+
+        if rc == 0:
+            return
+        msg = (self.lib.ou_last_error() or b"").decode()
+        if rc == L.STREAM_SHORT:
+            raise StreamShort(f"{what}: {msg}")
+        raise (L.OuRangeError if rc == 2 else L.OuHipError)(f"{what}: ouhip error {rc}: {msg}")
+
+    def open(self, seed=0, offset=0, channel=None):
+        got = ctypes.c_int(-1)
+        self._check(self.lib.ou_model_mux_channel_open(self.h, -1 if channel is None else int(channel), int(seed),
+                                                       int(offset), ctypes.byref(got)), "model_mux_channel_open")
+        return got.value
+
+    def room(self, c):
+        r = self.lib.ou_model_mux_room(self.h, int(c))
+        if r < 0:
+            self._check(int(r), "model_mux_room")
+        return int(r)
+
+    def push(self, c, x):
+        import torch
+
+        x = torch.as_tensor(x)
+        if x.ndim != 1 and x.numel() != x.shape[-1]:
+            raise ValueError("a stream is one mono signal: push (n,), (1, n) or (1, 1, n)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        x = x.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+        self._check(self.lib.ou_model_mux_push(self.h, int(c), x.data_ptr() if x.numel() else 0, x.numel(),
+                                               c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                    "model_mux_push")
+
+    def close(self, c):
+        self._check(self.lib.ou_model_mux_close(self.h, int(c)), "model_mux_close")
+
+    def bound(self, full_only=False):
+        counts, offsets = (ctypes.c_int64 * self.channels)(), (ctypes.c_int64 * self.channels)()
+        self._check(self.lib.ou_model_mux_bound(self.h, int(bool(full_only)), counts, offsets), "model_mux_bound")
+        return list(counts), list(offsets)
+
+    def run(self, full_only=False):
+        import torch
+
+        counts, offsets = self.bound(full_only)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty(sum(counts), dtype=torch.float32, device=dev)
+        got = (ctypes.c_int64 * self.channels)()
+        self._check(self.lib.ou_model_mux_run(self.h, int(bool(full_only)), out.data_ptr() if out.numel() else 0, got,
+                                              c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "model_mux_run")
+        assert list(got) == counts, (list(got), counts)
+        return [out[o:o + n] for o, n in zip(offsets, counts)]
+
+    def release(self):
+        if getattr(self, "h", None):
+            self.lib.ou_model_mux_destroy(self.h)
+            self.h = None
+            if getattr(self.bundle, "_mux", None) is self:
+                self.bundle._mux = None
 
     def __enter__(self):
         return self

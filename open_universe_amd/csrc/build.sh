@@ -21,7 +21,7 @@ cc() {   # cc <src> <obj> [extra flags...]
   /opt/rocm/bin/hipcc "${CFLAGS[@]}" ${OUHIP_CFLAGS:-} "$@" -c "$HERE/$src" -o "$OBJDIR/$obj" &
   pids+=($!)
 }
-for s in ou_gru.hip ou_misc.hip ou_program.hip ou_audio.hip ou_block.hip ou_rand.hip ou_model.hip ou_long.hip ou_pool.hip ou_stream.hip; do
+for s in ou_gru.hip ou_misc.hip ou_program.hip ou_audio.hip ou_block.hip ou_rand.hip ou_model.hip ou_long.hip ou_pool.hip ou_stream.hip ou_mux.hip; do
   cc "$s" "${s%.hip}.o"
 done
 cc ou_flac.cpp ou_flac.o   # host-only (FLAC input decoding for the CLI)

@@ -14,6 +14,13 @@
 // as a by-value table of at most kStreamSlots entries; a larger group is
 // several launches of the same call.  Sample positions are 64-bit; a window is
 // an int.  Every store is a plain vector store.
+//
+// ou_mux.hip includes this file with OU_STREAM_SHARED_ONLY defined and gets the
+// part both share -- the geometry checks and stream_emit_quad, the per-sample
+// rule of the overlap-add -- without the kernels and entry points below it.
+// (tests/test_emu_stream.py builds a copy of this file beside ou_common.h,
+// ou_normal.h and ou_philox.h alone, so the shared part lives here and not in
+// a header of its own.)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -71,6 +78,52 @@ __host__ __device__ __forceinline__ long long stream_start(const StreamGeom& g, 
     const long long s = (g.first + b) * g.hop;
     return g.closing && b == g.count - 1 && s > g.T - g.W ? g.T - g.W : s;
 }
+
+// Four output samples of one stream: out[m .. m + 3] are the samples t = first H
+// + m .. of the stream, t < t_end; w is the stream's first slot of this call,
+// carry its carry.  stream_overlap_add_kernel below states the rule; this is
+// its body, shared with mux_overlap_add_kernel (ou_mux.hip), which runs it once
+// per run of a channel's slots.
+__device__ __forceinline__ void stream_emit_quad(const float* __restrict__ w, long long w_bstride, const StreamGeom& g,
+                                                 const float* __restrict__ fade, float* __restrict__ carry,
+                                                 float* __restrict__ out, long long t_end, long long m)
+{
+    const long long t0 = g.first * g.hop;
+    if (t0 + m >= t_end) return;
+    const long long last = g.first + g.count - 1;
+    const long long last_start = g.count > 0 ? stream_start(g, g.count - 1) : 0;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    int nv = 0;
+    long long t = t0 + m, q = t / g.hop, u = t - q * g.hop;   // t = q H + u
+    for (int k = 0; k < 4; ++k, ++t) {
+        if (k && ++u == g.hop) u = 0, ++q;
+        if (t >= t_end) break;
+        const long long own = q < last ? q : last;
+        const long long uo = t - own * g.hop;                 // past the start of the owner's fade-in
+        if (own < g.first) {
+            a[k] = fmaf(1.f, carry[m + k], 0.f);   // count = 0: t - t0 < O
+        } else {
+            const float v = w[(own - g.first) * w_bstride + (t - (own == last ? last_start : own * g.hop))];
+            if (own >= 1 && uo < g.O) {
+                const float vp = own == g.first ? carry[uo] : w[(own - 1 - g.first) * w_bstride + uo + g.hop];
+                a[k] = fmaf(fade[uo], v, fmaf(fade[g.O + uo], vp, 0.f));
+            } else {
+                a[k] = fmaf(1.f, v, 0.f);
+            }
+        }
+        nv = k + 1;
+    }
+    if (nv == 4 && ((uintptr_t)(out + m) & 15) == 0) {
+        *reinterpret_cast<float4*>(out + m) = make_float4(a[0], a[1], a[2], a[3]);
+    } else {
+        for (int k = 0; k < nv; ++k) out[m + k] = a[k];
+    }
+    if (!g.closing)
+        for (int k = 0; k < 4; ++k)
+            if (m + k < g.O) carry[m + k] = w[(long long)(g.count - 1) * w_bstride + g.hop + m + k];
+}
+
+#ifndef OU_STREAM_SHARED_ONLY
 
 struct StreamTable {
     long long s[kStreamSlots];
@@ -152,43 +205,14 @@ __global__ void __launch_bounds__(256) stream_overlap_add_kernel(const float* __
                                                                  float* __restrict__ carry, float* __restrict__ out,
                                                                  long long t_end)
 {
-    const long long m = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
-    const long long t0 = g.first * g.hop;
-    if (t0 + m >= t_end) return;
-    const long long last = g.first + g.count - 1;
-    const long long last_start = g.count > 0 ? stream_start(g, g.count - 1) : 0;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    int nv = 0;
-    long long t = t0 + m, q = t / g.hop, u = t - q * g.hop;   // t = q H + u
-    for (int k = 0; k < 4; ++k, ++t) {
-        if (k && ++u == g.hop) u = 0, ++q;
-        if (t >= t_end) break;
-        const long long own = q < last ? q : last;
-        const long long uo = t - own * g.hop;                 // past the start of the owner's fade-in
-        if (own < g.first) {
-            a[k] = fmaf(1.f, carry[m + k], 0.f);   // count = 0: t - t0 < O
-        } else {
-            const float v = w[(own - g.first) * w_bstride + (t - (own == last ? last_start : own * g.hop))];
-            if (own >= 1 && uo < g.O) {
-                const float vp = own == g.first ? carry[uo] : w[(own - 1 - g.first) * w_bstride + uo + g.hop];
-                a[k] = fmaf(fade[uo], v, fmaf(fade[g.O + uo], vp, 0.f));
-            } else {
-                a[k] = fmaf(1.f, v, 0.f);
-            }
-        }
-        nv = k + 1;
-    }
-    if (nv == 4 && ((uintptr_t)(out + m) & 15) == 0) {
-        *reinterpret_cast<float4*>(out + m) = make_float4(a[0], a[1], a[2], a[3]);
-    } else {
-        for (int k = 0; k < nv; ++k) out[m + k] = a[k];
-    }
-    if (!g.closing)
-        for (int k = 0; k < 4; ++k)
-            if (m + k < g.O) carry[m + k] = w[(long long)(g.count - 1) * w_bstride + g.hop + m + k];
+    stream_emit_quad(w, w_bstride, g, fade, carry, out, t_end, ((long long)blockIdx.x * 256 + threadIdx.x) * 4);
 }
 
+#endif  // OU_STREAM_SHARED_ONLY
+
 }  // namespace
+
+#ifndef OU_STREAM_SHARED_ONLY
 
 extern "C" {
 
@@ -270,3 +294,5 @@ int ou_stream_overlap_add(const float* w, int64_t w_bstride, int window, int ove
 }
 
 }  // extern "C"
+
+#endif  // OU_STREAM_SHARED_ONLY

@@ -73,6 +73,8 @@ the grouping or the cuts of the pushes are.  The input lives in a ring of
 a shifted last window, which starts before ``m H``.  :class:`StreamCounts`
 is that arithmetic.
 """
+import collections
+
 import numpy as np
 
 DRAW_COUNTERS = 1 << 38         # Philox counters between two draws of a stream
@@ -320,3 +322,236 @@ class StreamCounts:
         """Samples a ``group`` step emits (``T``: the length at close)."""
         _, first, count, closing = step
         return (T if closing else (first + count) * H) - first * H
+
+
+# ---- multiplexed streams (DESIGN.md section 16; csrc/ou_mux.hip, mux.py) -----
+# C channels are streams as above, each with its own ring, carry, counts and
+# (seed, offset); W, O, H and the batch B of the plan are shared.  A push only
+# feeds a ring; run() pools the windows that are ready: the slot list is
+# [(c, i) for c ascending for i in pending(c)], group g its slots [g B, g B + B),
+# the unused slots of the last group repeating its last real slot.  A run is a
+# maximal stretch of consecutive slots of one channel in a group; a closing
+# channel with nothing left to run is a run without slots.  MuxCounts is that
+# arithmetic; MuxOverlapAdd restates what ou_mux_overlap_add computes.
+
+MuxRun = collections.namedtuple("MuxRun", "channel first count closing T slot out_off n")
+MuxGroup = collections.namedtuple("MuxGroup", "slots real runs")   # slots: B of (channel, window, start)
+MuxPlan = collections.namedtuple("MuxPlan", "slots groups counts offsets freed")
+
+FREE, OPEN, CLOSING = "free", "open", "closing"
+
+
+class MuxChannel:
+    def __init__(self):
+        self.state, self.fed, self.run, self.seed, self.offset = FREE, 0, 0, 0, 0
+
+
+class MuxCounts:
+    """The host arithmetic of ``C`` streams that share one batch-``B`` plan.
+    ``open`` / ``push`` / ``close`` change one channel's counts; ``plan_run``
+    lists what a ``run()`` does -- the slots, the groups with their runs, and
+    per channel the count of emitted samples and its offset in the one output
+    buffer (channel-major) -- and advances the counts; ``bound`` is the same
+    list without advancing.  Nothing here depends on the device, and the
+    grouping is a function of the sequence of calls alone."""
+
+    def __init__(self, W, O, B, C, Tp=None):
+        _, self.W, self.O = check(1, W, O)
+        if int(B) < 1 or int(C) < 1:
+            raise ValueError(f"batch {B} and channels {C} must be at least 1")
+        self.B, self.C, self.H = int(B), int(C), self.W - self.O
+        self.Tp = self.W if Tp is None else int(Tp)
+        self.cap = stream_ring(self.W, self.O, self.B)
+        self.ch = [MuxChannel() for _ in range(self.C)]
+
+    def _busy(self, c, what):
+        c = int(c)
+        if not 0 <= c < self.C:
+            raise ValueError(f"{what}: channel {c} of {self.C}")
+        if self.ch[c].state == FREE:
+            raise ValueError(f"{what}: channel {c} is free")
+        return c, self.ch[c]
+
+    def open(self, seed=0, offset=0, channel=None):
+        if not 0 <= int(seed) < 2**64 or not 0 <= int(offset) < 2**64:
+            raise ValueError("seed and offset are unsigned 64-bit integers")
+        if channel is None:
+            free = [c for c, s in enumerate(self.ch) if s.state == FREE]
+            if not free:
+                raise ValueError(f"open: all {self.C} channels are busy")
+            channel = free[0]
+        c = int(channel)
+        if not 0 <= c < self.C:
+            raise ValueError(f"open: channel {c} of {self.C}")
+        s = self.ch[c]
+        if s.state != FREE:
+            raise ValueError(f"open: channel {c} is {s.state}")
+        s.state, s.fed, s.run, s.seed, s.offset = OPEN, 0, 0, int(seed), int(offset)
+        return c
+
+    def ready(self, c):
+        s = self.ch[c]
+        return 0 if s.fed < self.W else (s.fed - self.W) // self.H + 1
+
+    def retain(self, c):
+        """The lowest position channel ``c``'s ring must still hold."""
+        s = self.ch[c]
+        return max(0, min(s.run * self.H, s.fed - self.W))
+
+    def held(self, c):
+        return max(0, self.ch[c].fed - self.cap)
+
+    def room(self, c):
+        c, s = self._busy(c, "room")
+        return self.cap - (s.fed - self.retain(c)) if s.state == OPEN else 0
+
+    def push(self, c, n):
+        """Feed ``n`` samples to channel ``c``: returns the position they start
+        at (they go to the ring at that position mod ``cap``).  More than
+        ``room(c)`` is refused whole."""
+        c, s = self._busy(c, "push")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"a push of {n} samples")
+        if s.state != OPEN:
+            raise ValueError(f"push: channel {c} is closing")
+        if n > self.room(c):
+            raise ValueError(f"push: {n} samples, channel {c} has room for {self.room(c)}: run() first")
+        if s.fed + n + self.Tp - self.W > STREAM_MAX_SAMPLES:
+            raise ValueError("the stream would pass 2^40 samples")
+        at = s.fed
+        s.fed += n
+        return at
+
+    def close(self, c):
+        c, s = self._busy(c, "close")
+        if s.state != OPEN:
+            raise ValueError(f"close: channel {c} is closing")
+        if s.fed < self.W:
+            raise StreamShort(f"channel {c}: a stream of {s.fed} samples is shorter than one window of {self.W}")
+        s.state = CLOSING
+
+    def pending(self, c):
+        """The windows of channel ``c`` that can run now."""
+        s = self.ch[c]
+        if s.state == FREE:
+            return range(0)
+        return range(s.run, n_windows(s.fed, self.W, self.O) if s.state == CLOSING else self.ready(c))
+
+    def _start(self, c, i):
+        s = self.ch[c]
+        return min(i * self.H, s.fed - self.W) if s.state == CLOSING else i * self.H
+
+    def _plan(self, full_only):
+        B, H = self.B, self.H
+        S = [(c, i) for c in range(self.C) for i in self.pending(c)]
+        if full_only:
+            S = S[:len(S) // B * B]
+        after = {c: s.run for c, s in enumerate(self.ch)}      # windows run, per channel, as the groups go by
+        counts, freed, groups = [0] * self.C, [], []
+        # closings with nothing left to run: the carry alone, ahead of every group
+        alone = []
+        for c, s in enumerate(self.ch):
+            if s.state == CLOSING and not len(self.pending(c)):
+                n = s.fed - s.run * H
+                assert n == self.O, (n, self.O)
+                alone.append([c, s.run, 0, 1, s.fed, 0, n])
+                counts[c] = n
+                freed.append(c)
+        raw = []
+        for g in range(0, len(S), B):
+            real = S[g:g + B]
+            runs = []
+            for b, (c, i) in enumerate(real):
+                if runs and runs[-1][0] == c:
+                    runs[-1][2] += 1
+                else:
+                    runs.append([c, i, 1, 0, 0, b, 0])
+            for r in runs:
+                c, s = r[0], self.ch[r[0]]
+                last = r[1] + r[2]
+                if s.state == CLOSING and last == n_windows(s.fed, self.W, self.O):
+                    r[3], r[4] = 1, s.fed
+                    freed.append(c)
+                r[6] = (s.fed if r[3] else last * H) - r[1] * H
+                counts[c] += r[6]
+                after[c] = last
+            raw.append((real, runs))
+        if alone:
+            if raw:
+                raw[0] = (raw[0][0], sorted(raw[0][1] + alone))
+            else:
+                raw.append(([], alone))
+        offsets = [sum(counts[:c]) for c in range(self.C)]
+        at = list(offsets)
+        for real, runs in raw:
+            slots = [(c, i, self._start(c, i)) for c, i in real]
+            slots += [slots[-1]] * (B - len(slots)) if slots else []
+            out = []
+            for c, first, count, closing, T, slot, n in runs:
+                out.append(MuxRun(c, first, count, closing, T, slot, at[c], n))
+                at[c] += n
+            groups.append(MuxGroup(slots, len(real), out))
+        return MuxPlan(S, groups, counts, offsets, sorted(freed)), after
+
+    def bound(self, full_only=False):
+        """(counts, offsets) of what ``run(full_only)`` would emit now, per
+        channel, in the one output buffer."""
+        plan, _ = self._plan(full_only)
+        return plan.counts, plan.offsets
+
+    def plan_run(self, full_only=False):
+        plan, after = self._plan(full_only)
+        for c, s in enumerate(self.ch):
+            s.run = after[c]
+        for c in plan.freed:
+            self.ch[c].__init__()
+        return plan
+
+
+class MuxOverlapAdd:
+    """What ou_mux_overlap_add computes, group by group in float32, with the
+    carries kept between the calls: ``run(plan, outs)`` takes the plan of one
+    ``run()`` and, per group, the ``(B, W)`` outputs of its slots, and returns
+    the per-channel samples.  Sample ``t`` of a run over windows ``[first,
+    first + count)`` belongs to window ``own = min(t // H, first + count - 1)``:
+    ``0 + 1 v`` outside the owner's fade-in, ``(0 + (1 - f) v_prev) + f v``
+    inside it, ``v_prev`` from the slot before inside the run and from the
+    channel's raw carry at the run's first window; a run that is not closing
+    then leaves the raw last ``O`` samples of its last window in the carry.
+    Here each product and sum is rounded (``overlap_add(dtype=float32)``); the
+    kernel fuses each ``+ w v`` as ou_stream_overlap_add does.  Carries and
+    outputs start as NaN, and padding slots are never read."""
+
+    def __init__(self, W, O, C):
+        self.W, self.O, self.H = int(W), int(O), int(W) - int(O)
+        self.tab = fade_table(self.O)
+        self.carry = np.full((int(C), self.O), np.nan, dtype=np.float32)
+
+    def run(self, plan, outs):
+        f32, W, O, H = np.float32, self.W, self.O, self.H
+        ys = [np.full(n, np.nan, dtype=f32) for n in plan.counts]
+        for grp, w in zip(plan.groups, outs):
+            w = np.asarray(w, dtype=f32)
+            for r in grp.runs:
+                last = r.first + r.count - 1
+                t_end = r.T if r.closing else (r.first + r.count) * H
+                last_start = min(last * H, r.T - W) if r.closing else last * H
+                y = ys[r.channel][r.out_off - plan.offsets[r.channel]:]
+                carry = self.carry[r.channel].copy()
+                for t in range(r.first * H, t_end):
+                    m = t - r.first * H
+                    own = min(t // H, last)
+                    u = t - own * H
+                    if own < r.first:
+                        y[m] = f32(0) + f32(1) * carry[m]
+                        continue
+                    v = w[r.slot + own - r.first, t - (last_start if own == last else own * H)]
+                    if own >= 1 and u < O:
+                        vp = carry[u] if own == r.first else w[r.slot + own - 1 - r.first, u + H]
+                        y[m] = (f32(0) + self.tab[1][u] * vp) + self.tab[0][u] * v
+                    else:
+                        y[m] = f32(0) + f32(1) * v
+                if not r.closing:
+                    self.carry[r.channel] = w[r.slot + r.count - 1, H:H + O]
+        return ys

@@ -479,6 +479,28 @@ class Universe(nn.Module):
         return ModelStream(self, window, overlap, batch=batch, n_steps=n_steps, epsilon=epsilon, keep_rms=keep_rms,
                            seed=seed, offset=offset)
 
+    def stream_mux(self, window: int, overlap: int, channels: int, batch: int = 8, n_steps: Optional[int] = None,
+                   epsilon: Optional[float] = None, keep_rms: Optional[bool] = False, **unsupported):
+        """Multiplexed streaming sessions (opt-in; mux.ModelMux, DESIGN.md
+        section 16): ``channels`` independent streams as in ``stream`` -- each
+        opened with its own ``(seed, offset)``, pushed at its own pace --
+        whose ready windows run together in the slots of the ``(batch,
+        window)`` plan ``enhance`` would record.  ``push(c, x)`` only feeds
+        channel ``c``'s ring; ``run()`` runs whatever windows are ready and
+        returns, per channel, the samples that became final.  ``target``,
+        ``use_aux_signal``, ``ensemble`` and ``warm_start`` are refused, as in
+        ``stream``."""
+        from ...mux import ModelMux
+
+        for k, v in unsupported.items():
+            if k in ("target", "fake_score_snr", "use_aux_signal", "ensemble", "ensemble_stat", "warm_start"):
+                if v is not None and v is not False and not (k == "ensemble_stat" and v == "median"):
+                    raise NotImplementedError(f"stream_mux does not support {k}")
+            else:
+                raise TypeError(f"stream_mux() got an unexpected keyword argument {k!r}")
+        return ModelMux(self, window, overlap, channels, batch=batch, n_steps=n_steps, epsilon=epsilon,
+                        keep_rms=keep_rms)
+
     def enhance_long_many(self, mixes, window: int, overlap: int, batch: int = 8, n_steps: Optional[int] = None,
                           epsilon: Optional[float] = None, rng: Optional[torch.Generator] = None,
                           keep_rms: Optional[bool] = False, pre_noise=None, **unsupported):
